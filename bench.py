@@ -2,7 +2,7 @@
 """Benchmark: CP tensor-regression fit_Adam iterations on MI355X (gfx950 HIP path).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--scaling weak|strong]
-                    [--no-cpu-baseline]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...   (N > 1)
 
 --scaling weak (default): every rank holds the config's per-GPU sample count (c4: 16384);
@@ -30,8 +30,17 @@ iterations than after 5 (tools/warmup_sweep.sh); the HBM-bound c2 kernel does no
 
 roofline: the dominant kernel (the single-pass X stream, k_linear_fused) timed with hipEvents on
 its own stream during the timed region; algorithmic bytes per launch = N*P*4 (X read once) +
-N*4 (y).  cpu_baseline: the oracle (a torch-CPU restatement of the reference's op sequence,
-oracle/cp_oracle.py) timed on this host on the same X for a bounded number of iterations.
+N*4 (y).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line
+(cpu_baseline: null).  --full adds what takes runs of its own after the timed steps:
+cpu_baseline, the oracle (a torch-CPU restatement of the reference's op sequence,
+oracle/cp_oracle.py) timed on this host on the same X for a bounded number of iterations, and at
+c7 the "hoststream" block (copy-only and compute-only timings).
+
+--dump-outputs DIR: what the timed fit_Adam left its caller after the last timed step, as
+DIR/<name>.npy (dump_outputs below).  The data, the planted model and the initial factors are
+seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -301,6 +310,25 @@ def host_stream_report(model, hs, Xres, y, fit, ms_step, dev):
             "overlap_hidden_frac": overlap, "chunk_rows": hs.chunk_rows, "bytes_per_step": nbytes}
 
 
+def dump_outputs(dirpath, model, n_timed):
+    """--dump-outputs: what a caller of the timed fit_Adam holds after its last step, one
+    DIR/<name>.npy each: the Kruskal factors (Bcp_<i>; spectral: Bcp_n_<i> and Bcp_c_<i>) and the
+    bias as the fit left them (float32), and the per-iteration losses the timed fit appended to
+    loss_running (float64, one per timed step).  A few hundred KB at every config."""
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {}
+    for attr in ("Bcp", "Bcp_n", "Bcp_c"):
+        for i, a in enumerate(getattr(model, attr, None) or []):
+            arrays[f"{attr}_{i}"] = a.detach().cpu().numpy().astype(np.float32)
+    bias = getattr(model, "bias", None)
+    if isinstance(bias, torch.Tensor):
+        arrays["bias"] = bias.detach().cpu().numpy().astype(np.float32)
+    arrays["loss_running"] = np.asarray(model.loss_running[len(model.loss_running) - n_timed:], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    log(f"bench: wrote {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values())} bytes) to {dirpath}")
+
+
 def launch_ranks(n, argv, json_out, timeout=None, cmd=None, grace=10.0):
     """Start the N ranks of `bench.py --gpus N` as child processes (torchrun's environment; the
     parent makes no HIP call: torch.cuda.device_count() does not initialise HIP on this image).
@@ -397,7 +425,13 @@ def main():
                     help="untimed fit_Adam iterations first: the compute-bound kernels (c3, c5) reach their "
                          "steady clock only after ~50 iterations (c3 kernel 0.402 ms after 5, 0.367 ms after 200)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what takes runs of its own: the CPU baseline (oracle on this "
+                         "host) and, for the out-of-core config c7, the copy-only / compute-only reference timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed fit left its caller (factors, bias, the timed "
+                         "steps' losses) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--allow-other-path", action="store_true",
                     help="measure even when the plan did not take the config's expected kernel path")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
@@ -539,6 +573,7 @@ def main():
     barrier()
     torch.cuda.synchronize()
     _ph("barrier + sync")
+    n_before = len(model.loss_running)
     t0 = time.perf_counter()
     fit(args.steps)
     torch.cuda.synchronize()
@@ -546,6 +581,11 @@ def main():
     el = time.perf_counter() - t0
     plan.set_timing(False)
     kt = plan.read_timing()
+    n_timed = len(model.loss_running) - n_before  # fit_Adam appends one loss per iteration it ran
+    if n_timed != args.steps:
+        raise SystemExit(f"bench {args.config}: the timed fit ran {n_timed} iterations, not --steps {args.steps}")
+    if args.dump_outputs and rank_id == 0:
+        dump_outputs(args.dump_outputs, model, n_timed)
     ar_samples = []
     if comm is not None:
         ar_samples = comm.read_timing()
@@ -623,7 +663,9 @@ def main():
                 ranks_block["note"] = "torch.distributed all_reduce path (TR_RCCL_DIRECT=0): no RCCL count / timing"
     ms_step = 1e3 * el / args.steps
     value = sum(rows_all) * args.steps / el
-    hoststream = host_stream_report(model, X, Xres, y, fit, ms_step, dev) if cfg.get("hoststream") else None
+    # runs of its own (copy only, compute only): --full
+    hoststream = (host_stream_report(model, X, Xres, y, fit, ms_step, dev)
+                  if cfg.get("hoststream") and args.full else None)
     achieved = bytes_launch / (dom_ms * 1e-3) / 1e9
     traffic = None
     traffic_src = None
@@ -670,6 +712,7 @@ def main():
     out["roofline"].update({"timed_launches": int(kt[dom][1]), "timing_every": max(1, args.timing_every)})
     if hoststream is not None:
         out["hoststream"] = hoststream
+    if cfg.get("hoststream"):
         out["data"] += "; X resident in pinned host memory, copied to HBM every step (inside the timed region)"
     if flops_launch is not None:
         # spectral: the roofline time is the larger of the HBM time of the algorithmic bytes and
@@ -701,7 +744,7 @@ def main():
             out["dtype"] = f"fp32 (GEMMs on bf16 pieces: X in {xp}, factors in three; fp32 accumulate)"
     if ranks_block is not None:
         out["ranks"] = ranks_block
-    if rank_id == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank_id == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline ...")
         out["cpu_baseline"] = cpu_baseline(cfg, Xres, y, init, args.cpu_budget, args.cpu_threads)
     else:

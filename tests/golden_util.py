@@ -25,9 +25,21 @@ def split(flat, shapes, dtype=np.float32):
     return out
 
 
+def _read(name):
+    """The arrays of <name>.npz, with an X_f32 kept beside it in row blocks (<name>.X_f32.<k>.npy:
+    a full-mantissa X too large for one committed file, tools/gen_golden.py save()) put back."""
+    d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    parts = []
+    while os.path.exists(os.path.join(GOLDEN, f"{name}.X_f32.{len(parts)}.npy")):
+        parts.append(np.load(os.path.join(GOLDEN, f"{name}.X_f32.{len(parts)}.npy")))
+    if parts:
+        d["X_f32"] = np.concatenate(parts)
+    return d
+
+
 def load(name):
     """A fixture with its factor lists split; float64 fixtures (f64_*) keep float64 inputs."""
-    d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    d = _read(name)
     meta = json.loads(str(d.pop("meta")))
     shapes = [tuple(s) for s in meta["factor_shapes"]]
     dt = np.float64 if meta.get("model") == "linear_f64" else np.float32
@@ -63,7 +75,7 @@ def normwise_rel(a, b):
 
 def load_spectral(name):
     """Spectral fixture: factor lists Bcp_n (I, Rn, 1) and Bcp_c (W, Rs, Cc), (D, Rs, 1), (n_out, Rs, 1)."""
-    d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    d = _read(name)
     meta = json.loads(str(d.pop("meta")))
     sn = [tuple(s) for s in meta["factor_shapes_n"]]
     sc = [tuple(s) for s in meta["factor_shapes_c"]]

@@ -94,6 +94,38 @@ def test_two_rank_line_schema():
     assert nothing["allreduce_us_per_step"] is None and nothing["allreduce_bytes"] == 64
 
 
+def test_dump_outputs_writes_what_the_fit_left(tmp_path):
+    """--dump-outputs: every factor and the bias as float32, the timed steps' losses (the last
+    n_timed entries of loss_running, not the warm-up's) as float64, one .npy each."""
+    import types
+    import numpy as np
+    import torch
+    bench = _bench()
+    g = torch.Generator().manual_seed(0)
+    lin = types.SimpleNamespace(Bcp=[torch.randn(5, 3, generator=g, requires_grad=True), torch.randn(4, 3, generator=g)],
+                                bias=torch.full((1,), 0.25, requires_grad=True), loss_running=[9.0, 8.0, 3.0, 2.0, 1.0])
+    out = tmp_path / "lin"
+    bench.dump_outputs(str(out), lin, 3)
+    assert sorted(p.name for p in out.iterdir()) == ["Bcp_0.npy", "Bcp_1.npy", "bias.npy", "loss_running.npy"]
+    for i, a in enumerate(lin.Bcp):
+        got = np.load(out / f"Bcp_{i}.npy")
+        assert got.dtype == np.float32
+        np.testing.assert_array_equal(got, a.detach().numpy())
+    np.testing.assert_array_equal(np.load(out / "bias.npy"), np.float32([0.25]))
+    losses = np.load(out / "loss_running.npy")
+    assert losses.dtype == np.float64
+    np.testing.assert_array_equal(losses, [3.0, 2.0, 1.0])
+    # spectral models hold two factor lists; multinomial ones no bias
+    spec = types.SimpleNamespace(Bcp_n=[torch.ones(2, 1, 1)], Bcp_c=[torch.ones(2, 1, 2), torch.ones(3, 1, 1)],
+                                 bias=torch.zeros(2), loss_running=[1.0])
+    bench.dump_outputs(str(tmp_path / "spec"), spec, 1)
+    assert sorted(p.name for p in (tmp_path / "spec").iterdir()) == [
+        "Bcp_c_0.npy", "Bcp_c_1.npy", "Bcp_n_0.npy", "bias.npy", "loss_running.npy"]
+    mnl = types.SimpleNamespace(Bcp=[torch.ones(2, 2)], loss_running=[0.5, 0.4])
+    bench.dump_outputs(str(tmp_path / "mnl"), mnl, 2)
+    assert sorted(p.name for p in (tmp_path / "mnl").iterdir()) == ["Bcp_0.npy", "loss_running.npy"]
+
+
 def test_launch_timeout_ends_a_hung_run(monkeypatch):
     """A rank that never finishes (and ignores SIGTERM) cannot hang the self-launched run: past
     --launch-timeout the parent terminates, then kills, the ranks and fails with no JSON line."""

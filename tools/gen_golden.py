@@ -40,7 +40,17 @@ def exact_X(rng, shape):
     return q, torch.tensor(q.astype(np.float32) / 8.0)
 
 
+PART_BYTES = 896 * 1024  # no committed file above 1 MiB
+
+
 def save(name, **arrays):
+    # a full-mantissa X of more than 1 MiB (it barely compresses) goes beside the .npz in row
+    # blocks, <name>.X_f32.<k>.npy; tests/golden_util.py puts them back together
+    X = arrays.get("X_f32")
+    if X is not None and X.nbytes > (1 << 20):
+        del arrays["X_f32"]
+        for k, blk in enumerate(np.array_split(X, -(-X.nbytes // PART_BYTES))):
+            np.save(os.path.join(OUT, f"{name}.X_f32.{k}.npy"), blk)
     path = os.path.join(OUT, name + ".npz")
     np.savez_compressed(path, **arrays)
     print("wrote", path, os.path.getsize(path), "bytes")

@@ -1,5 +1,5 @@
 # usage (GPU box): bash tools/profile_round.sh <tag> <config> [<config> ...]
-# Per config: one plain bench line, one rocprofv3 --kernel-trace --stats run, and two PMC passes
+# Per config: one bench line (--full: with the CPU baseline), one rocprofv3 --kernel-trace --stats run, and two PMC passes
 # (FETCH_SIZE, WRITE_SIZE separately, MI355X_MICROARCH.md HBM section), then tools/pmc_traffic.py
 # folds the counters into profiles/traffic.json. Every GPU step has its own time limit and the
 # script stops at the first failure.
@@ -21,7 +21,7 @@ for cfg in "$@"; do
     *) alg=""; dom=k_linear_fused ;;
   esac
   echo "[$cfg] bench" >&2
-  timeout -k 10 300 python $ROOT/bench.py --config $cfg --steps 30 --warmup 200 \
+  timeout -k 10 300 python $ROOT/bench.py --config $cfg --steps 30 --warmup 200 --full \
       > $OUT/${cfg}_bench.json 2> $OUT/${cfg}_bench.err || exit 1
   echo "[$cfg] kernel trace" >&2
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o $cfg -- \

@@ -12,8 +12,8 @@ fi
 timeout -k 10 900 python -u -m pytest ${@:-tests} -m gpu -x -v -s --timeout 300 --timeout-method thread \
     > $OUT/gputests.log 2>&1 || exit 1
 for c in c2 c3 c5; do
-  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 5 > $OUT/${c}_w5.json 2> $OUT/${c}_w5.err || exit 1
+  timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 5 --full > $OUT/${c}_w5.json 2> $OUT/${c}_w5.err || exit 1
 done
-timeout -k 10 600 python bench.py --config c4 --scaling strong --steps 20 --warmup 5 \
+timeout -k 10 600 python bench.py --config c4 --scaling strong --steps 20 --warmup 5 --full \
     > $OUT/c4strong_w5.json 2> $OUT/c4strong_w5.err || exit 1
 echo done
