@@ -50,11 +50,13 @@
 extern "C" {
 #endif
 
-#define TR_ABI_VERSION 8
+#define TR_ABI_VERSION 9
 
 #define TR_MODEL_LINEAR 0      /* CP_linear_regression: y_hat = <X, [[w; Phi]]> + bias, MSE */
 #define TR_MODEL_MULTINOMIAL 1 /* CP_logistic_regression: softmax(<X, [[w; Phi]]>), CE(weight) */
 #define TR_MODEL_SPECTRAL 2    /* spectral CP_linear_regression: lin_model + stepwise_spectral_model, MSE */
+
+#define TR_MODEL_CONV_SPECTRAL 3 /* convolutional spectral CP_linear_regression on the untiled (T, D) series */
 
 #define TR_MAX_FACTORS 8
 
@@ -311,6 +313,42 @@ int tr_plan_create_spectral(tr_plan** out, int device, int64_t n_w, int64_t n_d,
  */
 int tr_spectral_latents(tr_plan* plan, const float* X, int64_t n_rows, const float* params, float* out,
                         void* stream);
+
+/*
+ * Convolutional spectral model plan (ABI 9; convolutional_spectral_tensor_regression.
+ * CP_linear_regression, …py:750-877; model conv_linear :650-678 = conv :259-290 + complex_magnitude
+ * :292-303 + slmm_helper :426-430).  X is the untiled (T, n_d) fp32 series, y is (T, n_out); with
+ * T' = T - n_w + 1 and phi = softplus on flagged factors:
+ *   z[t,d,k] = sum_w X[t+w,d] phi(K)[w,k],  u = z (one component, signed) or ||z[t,d,s,:]||_2,
+ *   y_hat[t,n] = sum_r (sum_d u[t,d,r] phi(Bd)[d,r]) phi(Bo)[n,r] + bias[n],   t in [0, T')
+ *   n_w            temporal_window (odd);  n_complex = n_complex_dim + 1
+ *   max_series_rows  largest T later passed as n_rows
+ *   non_negative   host int32[3]: flags of (w, d, out); the w flag covers Kn and Ks
+ * Parameter arena (the reference's optimizer order Bcp_n + Bcp_w + [bias], each row-major):
+ *   Bd (n_d, R) | Bo (n_out, R) | Kn (n_w, Rn) | Ks (n_w, Rs, n_complex) | bias (n_out),  R = Rn + Rs
+ * tr_plan_factor_offset(plan, f) gives f = 0..3 and the bias offset for f = 4.
+ * With such a plan:
+ *   tr_forward     n_rows = T; out is (T' x n_out); weights is ignored (the reference's model never
+ *                  uses them) but must not be NULL
+ *   tr_loss_grad   n_rows = T; target = the T' x n_out block of y that starts at row n_w / 2
+ *                  (y[idx_conv]); norm = global T' * n_out; yhat_out (optional) is T' x n_out
+ *   tr_finalize_grad / tr_adam_step   ignore their lambda_l2 argument and take one lambda per
+ *                  factor group from tr_plan_set_l2_weights (required first): the total is
+ *                  loss + l[0] (||Kn|| + ||Ks||) + l[1] ||Bd|| + l[2] ||Bo|| (…py:1046); tr_adam_step
+ *                  also applies the NaN stop (…py:1059-1062) like a spectral plan
+ * Bad arguments (even or non-positive n_w, R outside 1..32, n_complex outside 1..4, n_out > 64,
+ * NULL pointers) return TR_E_ARG before any device call; shapes beyond the kernel's envelope
+ * (n_w > 257, n_d > 2^16, Rn + Rs * n_complex > 64) return TR_E_UNSUPPORTED with the reason in
+ * tr_last_error().  tr_plan_describe names the kernel form (path=conv-1pass-fmaf: one pass, fp32
+ * fmaf; X rows may start at any float offset and use any row stride >= n_d).
+ */
+int tr_plan_create_conv(tr_plan** out, int device, int64_t n_w, int64_t n_d, int64_t n_out, int rank_normal,
+                        int rank_spectral, int n_complex, int64_t max_series_rows, const int32_t* non_negative,
+                        float softplus_beta, float softplus_threshold);
+
+/* The conv plan's L2 weights: lambdas[3] = (w, d, out) as fit_Adam's lambda_L2 (host array, n = 3).
+ * TR_E_ARG on a NULL plan or a plan of another model. */
+int tr_plan_set_l2_weights(tr_plan* plan, const float* lambdas, int n);
 
 /*
  * Per-kernel device timing (measurement support; no reference counterpart).

@@ -487,6 +487,105 @@ class SpectralPlan(Plan):
         return out
 
 
+class ConvPlan(Plan):
+    """`tr_plan` of the convolutional spectral model (convolutional_spectral_tensor_regression.
+    CP_linear_regression): X is the untiled (T, D) series, arena = Bd (D, R) | Bo (N, R) | Kn (W, Rn) |
+    Ks (W, Rs, C) | bias (N).  `lambda_l2` of finalize_grad / adam_step is the length-3 sequence
+    (w, d, out) of the reference's fit_Adam."""
+
+    def __init__(self, n_w, n_d, n_out, rank_normal, rank_spectral, n_complex, max_rows, non_negative,
+                 softplus_kwargs, device):
+        self.lib = _lib.load()
+        self.dev = device_index(device)
+        self.device_str = f"cuda:{self.dev}"
+        self.model = _lib.TR_MODEL_CONV_SPECTRAL
+        self.dtype, self.f64, self._sfx = torch.float32, False, ""
+        self.dims = (int(n_w), int(n_d), int(n_out))
+        self.rank_normal, self.rank_spectral, self.n_complex = int(rank_normal), int(rank_spectral), int(n_complex)
+        self.max_rows = int(max_rows)
+        self.n_factors = 4
+        self.nonlin = nonlin_key(non_negative, softplus_kwargs, 3)
+        nn = (ctypes.c_int32 * 3)(*self.nonlin[0])
+        beta, thr = self.nonlin[1:]
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.dev):
+            rc = self.lib.tr_plan_create_conv(ctypes.byref(h), self.dev, self.dims[0], self.dims[1], self.dims[2],
+                                              self.rank_normal, self.rank_spectral, self.n_complex,
+                                              max(1, self.max_rows), nn, beta, thr)
+        check(rc, "tr_plan_create_conv")
+        self.h = h
+        _track(self)
+        self.num_params = int(self.lib.tr_plan_num_params(h))
+        self.num_grads = int(self.lib.tr_plan_num_grads(h))
+        self.offsets = [int(self.lib.tr_plan_factor_offset(h, f)) for f in range(5)]
+        self.describe = self.lib.tr_plan_describe(h).decode()
+        self._lam = None
+
+    def factor_shapes(self):
+        W, D, O = self.dims
+        Rn, Rs, Cc = self.rank_normal, self.rank_spectral, self.n_complex
+        return [(D, Rn + Rs), (O, Rn + Rs), (W, Rn), (W, Rs, Cc)]
+
+    def pack(self, Bcp_w, Bcp_n, bias):
+        """Bcp_w = [Kn (W, Rn), Ks (W, Rs, C) or (W, Rs)], Bcp_n = [Bd (D, R), Bo (N, R)], bias (N,)."""
+        facs = list(Bcp_n) + list(Bcp_w)
+        if len(Bcp_w) != 2 or len(Bcp_n) != 2:
+            raise ValueError(f"expected Bcp_w of 2 and Bcp_n of 2 factors, got {len(Bcp_w)} and {len(Bcp_n)}")
+        srcs = []
+        for f, (A, shp) in enumerate(zip(facs, self.factor_shapes())):
+            A = torch.as_tensor(A)
+            if int(np.prod(A.shape)) != int(np.prod(shp)) or tuple(A.shape[:2]) != tuple(shp[:2]):
+                raise ValueError(f"factor {f} has shape {tuple(A.shape)}, expected {shp}")
+            srcs.append(A.detach().reshape(-1))
+        srcs.append(torch.as_tensor(bias).detach().reshape(-1))
+        return _pack_arena(srcs, self.num_params, torch.float32, self.device_str)
+
+    def unpack_into(self, arena, Bcp_w, Bcp_n, bias=None):
+        _unpack_arena(arena, self.offsets, list(Bcp_n) + list(Bcp_w) + ([bias] if bias is not None else []))
+
+    def n_out_rows(self, T):
+        return int(T) - self.dims[0] + 1
+
+    def forward(self, X, arena, weights=None, out=None):
+        """conv_linear's y_hat, (T - W + 1, n_out)."""
+        if out is None:
+            out = torch.empty((self.n_out_rows(X.shape[0]), self.dims[2]), dtype=torch.float32, device=X.device)
+        self._set_stride(X)
+        rc = self.lib.tr_forward(self.h, ptr(X), X.shape[0], ptr(arena), ptr(arena), ptr(out),
+                                 stream_handle(self.dev))
+        check(rc, "tr_forward")
+        return out
+
+    def loss_grad(self, X, target, class_weight, norm, arena, weights, grad, yhat=None, stop=None):
+        """target: the (T - W + 1, n_out) block y[idx_conv], contiguous."""
+        self._set_stride(X)
+        rc = self.lib.tr_loss_grad(self.h, ptr(X), X.shape[0], ptr(target), None, float(norm), ptr(arena),
+                                   ptr(arena), ptr(grad), ptr(yhat), ptr(stop), stream_handle(self.dev))
+        check(rc, "tr_loss_grad")
+
+    def set_l2(self, lambda_l2):
+        lam = tuple(float(lambda_l2[i]) for i in range(3))
+        if lam != self._lam:
+            arr = (ctypes.c_float * 3)(*lam)
+            check(self.lib.tr_plan_set_l2_weights(self.h, arr, 3), "tr_plan_set_l2_weights")
+            self._lam = lam
+
+    def finalize_grad(self, arena, grad, lambda_l2, grad_total, loss_out):
+        self.set_l2(lambda_l2)
+        rc = self.lib.tr_finalize_grad(self.h, ptr(arena), ptr(grad), 0.0, ptr(grad_total), ptr(loss_out),
+                                       stream_handle(self.dev))
+        check(rc, "tr_finalize_grad")
+
+    def adam_step(self, arena, grad, m, v, vmax, lambda_l2, hp, step, hist, hist_base, it, patience, tol,
+                  stop):
+        self.set_l2(lambda_l2)
+        rc = self.lib.tr_adam_step(self.h, ptr(arena), ptr(grad), ptr(m), ptr(v), ptr(vmax), 0.0,
+                                   hp["lr"], hp["beta1"], hp["beta2"], hp["eps"], hp["weight_decay"],
+                                   1 if hp["amsgrad"] else 0, int(step), ptr(hist), int(hist_base), int(it),
+                                   int(patience), float(tol), ptr(stop), stream_handle(self.dev))
+        check(rc, "tr_adam_step")
+
+
 def _rows_contiguous(X):
     """Each X[n] block is contiguous (any stride, even overlapping, along dim 0)."""
     expect = 1

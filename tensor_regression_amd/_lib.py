@@ -13,11 +13,12 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TR_HIP_LIB", os.path.join(_HERE, "libtr_hip.so"))
 
-TR_ABI_VERSION = 8
+TR_ABI_VERSION = 9
 TR_STOP_DEVICE_ERROR = -(1 << 30)
 TR_MODEL_LINEAR = 0
 TR_MODEL_MULTINOMIAL = 1
 TR_MODEL_SPECTRAL = 2
+TR_MODEL_CONV_SPECTRAL = 3
 TR_MAX_FACTORS = 8
 KERNEL_KINDS = ["stream_fused", "stream_rows", "stream_cols", "reduce", "mttkrp", "prep", "update"]
 
@@ -47,6 +48,10 @@ SIGNATURES = {
     "tr_plan_create_spectral": (_c.c_int, [_c.POINTER(_vp), _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int,
                                            _c.c_int, _c.c_int, _c.c_int64, _c.POINTER(_c.c_int32), _c.c_float,
                                            _c.c_float]),
+    "tr_plan_create_conv": (_c.c_int, [_c.POINTER(_vp), _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int,
+                                       _c.c_int, _c.c_int, _c.c_int64, _c.POINTER(_c.c_int32), _c.c_float,
+                                       _c.c_float]),
+    "tr_plan_set_l2_weights": (_c.c_int, [_vp, _c.POINTER(_c.c_float), _c.c_int]),
     "tr_spectral_latents": (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _vp, _vp]),
     "tr_plan_set_x_stride": (_c.c_int, [_vp, _c.c_int64]),
     "tr_x_range": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _vp, _c.c_int, _vp]),

@@ -1,0 +1,594 @@
+// tr_conv.hip — convolutional spectral CP regression on the untiled (T, D) series
+// (convolutional_spectral_tensor_regression.py: conv 259-290, complex_magnitude 292-303,
+// slmm_helper 426-430, conv_linear 650-678, L2_penalty 700-718).
+//
+//   z[t,d,k]  = sum_w X[t+w,d] * Kp[w,k]            k over the K = Rn + Rs*C kernel columns
+//   u[t,d,r]  = z (signed) for a one-component rank, ||z[t,d,s,:]||_2 for a spectral rank
+//   q[t,r]    = sum_d u[t,d,r] * Bd[d,r]
+//   y_hat     = q . Bo^T + bias,  loss = mean (y_hat - y)^2
+//
+// k_conv<1>: one workgroup of 256 threads owns tiles of TT = 256 consecutive output times over
+// all of D.  The (TT + W - 1) x DC slab of X is staged in LDS transposed (column-major, odd
+// pitch: the strided writes and the time-contiguous reads are both conflict free), D in chunks
+// of DC columns when the slab does not fit.
+//   phase A   thread = one output time, its columns serial: z for one group of 16 kernel columns
+//             at a time (16 accumulators; the kernel row Kp[g][w][0..15] is wave-uniform), then
+//             u and q.  q stays thread-private (LDS row of the thread): no cross-lane reduction.
+//   epilogue  y_hat, squared error (double), e = 2 (y_hat - y) / (T' N) to a global scratch,
+//             dBo / dbias by one thread per entry over the tile's times, dq = e . Bo in place of q.
+//   phase B   wave = every fourth column of the chunk, its lanes the times of one 64-time
+//             subtile after another: z recomputed from the slab still in LDS, dBd by one wave
+//             butterfly per (column, group), dz to a wave-private LDS tile, then the same wave
+//             with lanes = kernel taps w (and, for W < 64, 64 / W' time sub-ranges) accumulates
+//             dKp[w, k] += X[t + w, d] dz[t, d, k] in registers.  Per group the four waves'
+//             accumulators are summed in a fixed order.
+// Every workgroup adds into its own gradient slab (same thread, same order every time);
+// k_conv_finish sums the slabs in index order and applies the softplus chain.  No float atomics:
+// two runs on the same inputs are bitwise equal.
+// k_conv<0> is phase A + y_hat only (predict).
+//
+// Form: fp32 fmaf on the VALU throughout ("conv-1pass-fmaf").  Bounds: every LDS index is
+// < DC*XP + 256*QP + 4*64*16 (conv_geom_init sizes the allocation from the same terms); slab rows
+// beyond T are zero-filled and times >= T' contribute e = 0.
+#include <cstring>
+
+#include "tr_conv.h"
+
+namespace tr {
+
+namespace {
+constexpr int QP = CONV_MAXR + 1;          // LDS pitch of a q / dq row
+constexpr int DZ_FLOATS = 4 * 64 * CONV_KC;  // four wave-private dz tiles
+constexpr int LDS_BUDGET_FLOATS = 38912;     // 152 KiB of the CU's 160 KiB
+
+__device__ __forceinline__ void wave_lds_sync() {
+  // the wave's own LDS writes before its lanes read each other's (one wave executes in lockstep;
+  // the fences keep the compiler from moving the accesses across)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// z[0..15] of one (time, column): the slab column at xp, the group's kernel rows at kp
+__device__ __forceinline__ void conv_z(const float* __restrict__ xp, const float* __restrict__ kp, int W,
+                                       float (&z)[CONV_KC]) {
+#pragma unroll
+  for (int j = 0; j < CONV_KC; ++j) z[j] = 0.f;
+#pragma unroll 2
+  for (int w = 0; w < W; ++w) {
+    const float x = xp[w];
+#pragma unroll
+    for (int j = 0; j < CONV_KC; ++j) z[j] = fmaf(x, kp[w * CONV_KC + j], z[j]);
+  }
+}
+
+template <int CC>
+__device__ __forceinline__ float conv_mag(const float (&z)[CONV_KC], int j) {
+  if (CC == 1) return z[j];
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < CC; ++c) s = fmaf(z[j * CC + c], z[j * CC + c], s);
+  return sqrtf(s);
+}
+
+// phase A of one column group: q[t, rbase + j] += sum_d u[t, d, j] Bd[d, rbase + j]
+template <int CC>
+__device__ __forceinline__ void conv_a_group(const float* sX, float* sQrow, const float* __restrict__ kp,
+                                             const float* __restrict__ bd, int R, int nr, int W, int XP, int dc,
+                                             int tid) {
+  constexpr int RPG = CONV_KC / CC;
+  float qa[RPG];
+#pragma unroll
+  for (int j = 0; j < RPG; ++j) qa[j] = 0.f;
+  for (int dl = 0; dl < dc; ++dl) {
+    float z[CONV_KC];
+    conv_z(sX + dl * XP + tid, kp, W, z);
+#pragma unroll
+    for (int j = 0; j < RPG; ++j) {
+      const float b = j < nr ? bd[(int64_t)dl * R + j] : 0.f;
+      qa[j] = fmaf(conv_mag<CC>(z, j), b, qa[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < RPG; ++j)
+    if (j < nr) sQrow[j] += qa[j];
+}
+
+// phase B of one column group (see the header comment); contains workgroup barriers: every wave
+// of the workgroup calls it with the same (dc, W, group)
+template <int CC>
+__device__ __forceinline__ void conv_b_group(const float* sX, const float* sDQ, float* sDZ,
+                                             const float* __restrict__ kp, const float* __restrict__ bdp,
+                                             float* slabBd, float* slabK, int R, int nr, int W, int XP, int dc,
+                                             int tid) {
+  constexpr int RPG = CONV_KC / CC;
+  constexpr int NPMAX = (CONV_MAXW + 63) / 64;
+  const int lane = tid & 63, wv = tid >> 6;
+  const int npass = (W + 63) / 64;
+  int WL = 64;
+  if (W < 64) {
+    WL = 1;
+    while (WL < W) WL <<= 1;
+  }
+  const int NTS = 64 / WL;  // time sub-ranges of a subtile; each WL times long
+  const int wl = lane & (WL - 1), ts = lane / WL;
+  float acc[NPMAX][CONV_KC];
+#pragma unroll
+  for (int p = 0; p < NPMAX; ++p)
+#pragma unroll
+    for (int k = 0; k < CONV_KC; ++k) acc[p][k] = 0.f;
+  float* myDZ = sDZ + wv * 64 * CONV_KC;
+  for (int dl = wv; dl < dc; dl += 4) {
+    float bd[RPG], bdv[RPG];
+#pragma unroll
+    for (int j = 0; j < RPG; ++j) {
+      bd[j] = 0.f;
+      bdv[j] = j < nr ? bdp[(int64_t)dl * R + j] : 0.f;
+    }
+    for (int tsb = 0; tsb < CONV_TT / 64; ++tsb) {
+      const int tl = tsb * 64 + lane;
+      float z[CONV_KC], dz[CONV_KC];
+      conv_z(sX + dl * XP + tl, kp, W, z);
+#pragma unroll
+      for (int k = 0; k < CONV_KC; ++k) dz[k] = 0.f;
+#pragma unroll
+      for (int j = 0; j < RPG; ++j) {
+        const float dqv = j < nr ? sDQ[tl * QP + j] : 0.f;
+        const float m = conv_mag<CC>(z, j);
+        bd[j] = fmaf(m, dqv, bd[j]);
+        if (CC == 1) {
+          dz[j] = dqv * bdv[j];
+        } else {
+          // d||z|| / dz = z / ||z||, 0 where ||z|| = 0 (torch.norm's backward)
+          const float cf = m > 0.f ? dqv * bdv[j] / m : 0.f;
+#pragma unroll
+          for (int c = 0; c < CC; ++c) dz[j * CC + c] = cf * z[j * CC + c];
+        }
+      }
+      float4* wr = reinterpret_cast<float4*>(myDZ + lane * CONV_KC);
+#pragma unroll
+      for (int k4 = 0; k4 < CONV_KC / 4; ++k4)
+        wr[k4] = make_float4(dz[4 * k4], dz[4 * k4 + 1], dz[4 * k4 + 2], dz[4 * k4 + 3]);
+      wave_lds_sync();
+      for (int tt = ts * WL; tt < ts * WL + WL; ++tt) {
+        float dzv[CONV_KC];
+        const float4* rd = reinterpret_cast<const float4*>(myDZ + tt * CONV_KC);
+#pragma unroll
+        for (int k4 = 0; k4 < CONV_KC / 4; ++k4) {
+          const float4 v = rd[k4];
+          dzv[4 * k4] = v.x;
+          dzv[4 * k4 + 1] = v.y;
+          dzv[4 * k4 + 2] = v.z;
+          dzv[4 * k4 + 3] = v.w;
+        }
+        const float* xb = sX + dl * XP + tsb * 64 + tt;
+#pragma unroll
+        for (int p = 0; p < NPMAX; ++p) {
+          if (p < npass) {
+            const int w = p * 64 + wl;
+            const float x = w < W ? xb[w] : 0.f;
+#pragma unroll
+            for (int k = 0; k < CONV_KC; ++k) acc[p][k] = fmaf(x, dzv[k], acc[p][k]);
+          }
+        }
+      }
+      wave_lds_sync();
+    }
+#pragma unroll
+    for (int j = 0; j < RPG; ++j) {
+      const float s = tr_wave_allreduce(bd[j]);
+      if (lane == j && j < nr) slabBd[(int64_t)dl * R + j] += s;
+    }
+  }
+  // the four waves' (and the time sub-ranges') dKp partials, summed in a fixed order
+#pragma unroll
+  for (int p = 0; p < NPMAX; ++p) {
+    if (p < npass) {
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < CONV_KC; ++k) myDZ[lane * CONV_KC + k] = acc[p][k];
+      __syncthreads();
+      for (int o = tid; o < WL * CONV_KC; o += CONV_TT) {
+        const int wlo = o / CONV_KC, k = o - wlo * CONV_KC;
+        const int w = p * 64 + wlo;
+        if (w < W) {
+          float s = 0.f;
+          for (int v = 0; v < 4; ++v)
+            for (int u = 0; u < NTS; ++u) s += sDZ[(v * 64 + u * WL + wlo) * CONV_KC + k];
+          slabK[w * CONV_KC + k] += s;
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+}  // namespace
+
+template <int TRAIN>
+__global__ __launch_bounds__(CONV_TT) void k_conv(ConvGeom g, const float* __restrict__ X, int64_t T, int64_t xld,
+                                                  const float* __restrict__ phi, const float* __restrict__ params,
+                                                  const float* __restrict__ Kp, const float* __restrict__ y,
+                                                  float scale, float* gpart, double* __restrict__ dpart,
+                                                  float* ebuf, float* __restrict__ yhat,
+                                                  const int32_t* __restrict__ stop) {
+  if (stop != nullptr && *stop != 0) return;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int XP = g.XP, W = g.W, R = g.R, N = g.N, D = g.D, DC = g.DC;
+  float* sDZ = lds;  // first: 16-byte aligned for the float4 accesses
+  float* sQ = sDZ + DZ_FLOATS;
+  float* sX = sQ + CONV_TT * QP;
+  const int tid = threadIdx.x;
+  const int64_t Tp = T - W + 1;
+  const int64_t ntiles = (Tp + CONV_TT - 1) / CONV_TT;
+  const int nchunks = (D + DC - 1) / DC;
+  const int rows = CONV_TT + W - 1;
+  const float* pBd = phi + g.offBd;
+  const float* pBo = phi + g.offBo;
+  const float* bias = params + g.offB;
+  float* slab = TRAIN ? gpart + (int64_t)blockIdx.x * g.slab : nullptr;
+  double lossacc = 0.0;
+
+  auto stage = [&](int64_t t0, int d0, int dc) {
+    const int n = rows * dc;
+    for (int idx = tid; idx < n; idx += CONV_TT) {
+      const int row = idx / dc, dl = idx - row * dc;
+      const int64_t t = t0 + row;
+      sX[dl * XP + row] = t < T ? X[t * xld + d0 + dl] : 0.f;
+    }
+  };
+
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t t0 = tile * CONV_TT;
+    const int64_t t = t0 + tid;
+    const bool valid = t < Tp;
+    for (int r = 0; r < R; ++r) sQ[tid * QP + r] = 0.f;
+    for (int c = 0; c < nchunks; ++c) {
+      const int d0 = c * DC, dc = D - d0 < DC ? D - d0 : DC;
+      __syncthreads();  // the slab's previous readers are done
+      stage(t0, d0, dc);
+      __syncthreads();
+      for (int gi = 0; gi < g.G; ++gi) {
+        const ConvGroup gr = g.grp[gi];
+        const float* kp = Kp + (int64_t)gi * W * CONV_KC;
+        const float* bd = pBd + (int64_t)d0 * R + gr.rbase;
+        float* qrow = sQ + tid * QP + gr.rbase;
+        switch (gr.cc) {
+          case 1: conv_a_group<1>(sX, qrow, kp, bd, R, gr.nr, W, XP, dc, tid); break;
+          case 2: conv_a_group<2>(sX, qrow, kp, bd, R, gr.nr, W, XP, dc, tid); break;
+          case 3: conv_a_group<3>(sX, qrow, kp, bd, R, gr.nr, W, XP, dc, tid); break;
+          default: conv_a_group<4>(sX, qrow, kp, bd, R, gr.nr, W, XP, dc, tid); break;
+        }
+      }
+    }
+    // epilogue: y_hat, squared error, residual
+    for (int n = 0; n < N; ++n) {
+      float yh = 0.f;
+      for (int r = 0; r < R; ++r) yh = fmaf(sQ[tid * QP + r], pBo[n * R + r], yh);
+      yh += bias[n];
+      if (valid) {
+        if (yhat != nullptr) yhat[t * N + n] = yh;
+        if (TRAIN) {
+          const float diff = yh - y[t * N + n];
+          lossacc += (double)diff * (double)diff;
+          ebuf[t * N + n] = scale * diff;
+        }
+      }
+    }
+    if (!TRAIN) continue;
+    __syncthreads();  // e (global scratch) and q (LDS) of every time of the tile
+    const int nvalid = Tp - t0 < CONV_TT ? (int)(Tp - t0) : CONV_TT;
+    for (int p = tid; p < N * R; p += CONV_TT) {
+      const int n = p / R, r = p - n * R;
+      float s = 0.f;
+      for (int tl = 0; tl < nvalid; ++tl) s = fmaf(ebuf[(t0 + tl) * N + n], sQ[tl * QP + r], s);
+      slab[g.sOffBo + p] += s;
+    }
+    for (int n = tid; n < N; n += CONV_TT) {
+      float s = 0.f;
+      for (int tl = 0; tl < nvalid; ++tl) s += ebuf[(t0 + tl) * N + n];
+      slab[g.sOffB + n] += s;
+    }
+    __syncthreads();  // q has been read: dq = e . Bo takes its place
+    for (int r = 0; r < R; ++r) {
+      float s = 0.f;
+      if (valid)
+        for (int n = 0; n < N; ++n) s = fmaf(ebuf[t * N + n], pBo[n * R + r], s);
+      sQ[tid * QP + r] = s;
+    }
+    __syncthreads();
+    for (int c = nchunks - 1; c >= 0; --c) {  // the last chunk is still in LDS
+      const int d0 = c * DC, dc = D - d0 < DC ? D - d0 : DC;
+      if (c != nchunks - 1) {
+        __syncthreads();
+        stage(t0, d0, dc);
+        __syncthreads();
+      }
+      for (int gi = 0; gi < g.G; ++gi) {
+        const ConvGroup gr = g.grp[gi];
+        const float* kp = Kp + (int64_t)gi * W * CONV_KC;
+        const float* bd = pBd + (int64_t)d0 * R + gr.rbase;
+        float* sBd = slab + g.sOffBd + (int64_t)d0 * R + gr.rbase;
+        float* sK = slab + g.sOffK + (int64_t)gi * W * CONV_KC;
+        const float* dq = sQ + gr.rbase;
+        switch (gr.cc) {
+          case 1: conv_b_group<1>(sX, dq, sDZ, kp, bd, sBd, sK, R, gr.nr, W, XP, dc, tid); break;
+          case 2: conv_b_group<2>(sX, dq, sDZ, kp, bd, sBd, sK, R, gr.nr, W, XP, dc, tid); break;
+          case 3: conv_b_group<3>(sX, dq, sDZ, kp, bd, sBd, sK, R, gr.nr, W, XP, dc, tid); break;
+          default: conv_b_group<4>(sX, dq, sDZ, kp, bd, sBd, sK, R, gr.nr, W, XP, dc, tid); break;
+        }
+      }
+    }
+  }
+  if (TRAIN) {
+    __shared__ double wl[CONV_TT / 64];
+    const double s = tr_wave_allreduce_d(lossacc);
+    if ((tid & 63) == 0) wl[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) dpart[blockIdx.x] = (wl[0] + wl[1]) + (wl[2] + wl[3]);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_conv_kp(int n, const float* __restrict__ phi,
+                                                 const int32_t* __restrict__ kmap, float* __restrict__ Kp,
+                                                 const int32_t* __restrict__ stop) {
+  if (stop != nullptr && *stop != 0) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int32_t src = kmap[i];
+  Kp[i] = src >= 0 ? phi[src] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_conv_finish(int64_t nparams, int64_t nfelem, int nslabs, int64_t slab,
+                                                     const float* __restrict__ gpart,
+                                                     const double* __restrict__ dpart,
+                                                     const int32_t* __restrict__ gmap,
+                                                     const float* __restrict__ dphi, double loss_scale,
+                                                     float* __restrict__ grad_out,
+                                                     const int32_t* __restrict__ stop) {
+  if (stop != nullptr && *stop != 0) return;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < nparams) {
+    const int64_t src = gmap[e];
+    float s = 0.f;
+    for (int b = 0; b < nslabs; ++b) s += gpart[(int64_t)b * slab + src];
+    grad_out[e] = e < nfelem ? s * dphi[e] : s;
+  } else if (e == nparams) {
+    double l = 0.0;
+    for (int b = 0; b < nslabs; ++b) l += dpart[b];
+    grad_out[nparams] = (float)(l * loss_scale);
+    grad_out[nparams + 1] = 0.f;
+  }
+}
+
+// The update of the convolutional model: k_update's arithmetic (tr_update.hip) with one lambda per
+// factor and the reference's order of the penalty sum,
+//   loss + L2_penalty(Bcp_w, [l0, l0]) + L2_penalty(Bcp_n, l[1:])        (…py:1046)
+// A kernel of its own: k_update as compiled for the other models is untouched.
+struct ConvLam {
+  float v[4];  // by arena factor: Bd, Bo, Kn, Ks
+};
+
+__global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, ConvLam lam, float* __restrict__ params,
+                                                      const float* __restrict__ grad, UpdateArgs ua,
+                                                      float* __restrict__ m, float* __restrict__ v,
+                                                      float* __restrict__ vmax, float* __restrict__ grad_total_out,
+                                                      float* __restrict__ loss_out, double* __restrict__ loss_hist,
+                                                      int32_t* __restrict__ stop) {
+#pragma clang fp contract(off)
+  __shared__ float wsum[4 * 16];
+  __shared__ float norms[4];
+  __shared__ float coef[4];
+  const int t = threadIdx.x, lane = t & 63, q = t >> 6;
+  const int64_t nfe = fs.nfelem, np = nfe + n_bias;
+  const bool checked = ua.mode == 0 && stop != nullptr;
+  const int32_t stop0 = stop != nullptr ? *stop : 0;
+  const float status = checked ? grad[np + 1] : 0.f;
+  auto factor_of = [&](int64_t e) {
+    int f = 0;
+#pragma unroll
+    for (int g = 1; g < 4; ++g)
+      if (e >= fs.off[g]) f = g;
+    return f;
+  };
+  float accn[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t k = t; k < nfe; k += 1024) {
+    const float a = params[k];
+    const int f = factor_of(k);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
+  }
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const float r = tr_wave_allreduce(accn[f]);
+    if (lane == 0) wsum[f * 16 + q] = r;
+  }
+  __syncthreads();
+  if (t < 4) {
+    float tot = 0.f;
+    for (int w = 0; w < 16; ++w) tot += wsum[t * 16 + w];
+    norms[t] = sqrtf(tot);
+    coef[t] = lam.v[t] / (2.0f * norms[t]);
+  }
+  __syncthreads();
+  if (stop0 != 0) return;
+  if (checked && status != 0.0f) {
+    if (t == 0) *stop = TR_STOP_DEVICE_ERROR - (int32_t)ua.iter;
+    return;
+  }
+  const bool adam = ua.mode != 1;
+  const bool ams = adam && ua.amsgrad;
+  for (int64_t e = t; e < np; e += 1024) {
+    float g = grad[e], p = params[e];
+    if (e < nfe) g = g + coef[factor_of(e)] * (2.0f * p);
+    if (!adam) {
+      grad_total_out[e] = g;
+      continue;
+    }
+    float mm = m[e], vv = v[e], vm = ams ? vmax[e] : 0.f;
+    g = ua.weight_decay != 0.0f ? fmaf(p, ua.weight_decay, g) : g;
+    mm = fmaf(ua.one_minus_b1, g - mm, mm);
+    vv = vv * ua.beta2;
+    vv = vv + ua.one_minus_b2 * g * g;
+    vm = fmaxf(vm, vv);
+    if (ams) vmax[e] = vm;
+    const float denom = sqrtf(ams ? vm : vv) / ua.bc2_sqrt + ua.eps;
+    p = p + (-ua.step_size) * (mm / denom);
+    m[e] = mm;
+    v[e] = vv;
+    params[e] = p;
+  }
+  if (t == 0) {
+    const float pw = (0.f + norms[2] * lam.v[2]) + norms[3] * lam.v[3];
+    const float pn = (0.f + norms[0] * lam.v[0]) + norms[1] * lam.v[1];
+    const float total = (grad[np] + pw) + pn;
+    if (loss_out != nullptr) *loss_out = total;
+    if (ua.mode == 0 && loss_hist != nullptr) loss_hist[ua.hist_base + ua.iter] = (double)total;
+    if (ua.mode == 0 && ua.nan_stop && stop != nullptr && ua.iter <= ua.patience && __builtin_isnan(total))
+      *stop = -(int32_t)(ua.iter + 1);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+bool conv_geom_init(ConvGeom* g, int64_t n_w, int64_t n_d, int64_t n_out, int rank_normal, int rank_spectral,
+                    int n_complex, const int32_t* non_negative, std::string* why) {
+  std::memset(g, 0, sizeof(*g));
+  auto no = [&](const char* m) {
+    *why = m;
+    return false;
+  };
+  if (n_w > CONV_MAXW) return no("temporal window beyond the conv kernel's envelope (W <= 257)");
+  if (n_d > 65536) return no("n_d beyond the conv kernel's envelope (D <= 65536)");
+  if (n_out > CONV_MAXN) return no("n_out beyond the conv kernel's envelope (N <= 64)");
+  if (rank_normal + rank_spectral > CONV_MAXR)
+    return no("rank_normal + rank_spectral beyond the conv kernel's envelope (R <= 32)");
+  if (n_complex > CONV_MAXC) return no("n_complex beyond the conv kernel's envelope (C <= 4)");
+  if (rank_normal + rank_spectral * n_complex > CONV_MAXK)
+    return no("rank_normal + rank_spectral * n_complex beyond the conv kernel's envelope (K <= 64)");
+  g->W = (int)n_w;
+  g->D = (int)n_d;
+  g->N = (int)n_out;
+  g->Rn = rank_normal;
+  g->Rs = rank_spectral;
+  g->C = n_complex;
+  g->R = rank_normal + rank_spectral;
+  g->K = rank_normal + rank_spectral * n_complex;
+  for (int i = 0; i < 3; ++i) g->nonneg[i] = non_negative != nullptr && non_negative[i] ? 1 : 0;
+  g->offBd = 0;
+  g->offBo = g->offBd + (int64_t)g->D * g->R;
+  g->offKn = g->offBo + (int64_t)g->N * g->R;
+  g->offKs = g->offKn + (int64_t)g->W * g->Rn;
+  g->offB = g->offKs + (int64_t)g->W * g->Rs * g->C;
+  g->nparams = g->offB + g->N;
+  // column groups: one-component ranks (normal, and spectral when C == 1) 16 to a group, then
+  // spectral ranks 16 / C to a group
+  const int n1 = g->C == 1 ? g->R : g->Rn;
+  int G = 0;
+  for (int r = 0; r < n1; r += CONV_KC) {
+    g->grp[G].cc = 1;
+    g->grp[G].rbase = r;
+    g->grp[G].nr = n1 - r < CONV_KC ? n1 - r : CONV_KC;
+    ++G;
+  }
+  if (g->C > 1) {
+    const int rpg = CONV_KC / g->C;
+    for (int s = 0; s < g->Rs; s += rpg) {
+      if (G >= CONV_MAXG) return no("too many kernel column groups");
+      g->grp[G].cc = g->C;
+      g->grp[G].rbase = g->Rn + s;
+      g->grp[G].nr = g->Rs - s < rpg ? g->Rs - s : rpg;
+      ++G;
+    }
+  }
+  g->G = G;
+  g->sOffBd = 0;
+  g->sOffBo = g->sOffBd + (int64_t)g->D * g->R;
+  g->sOffK = g->sOffBo + (int64_t)g->N * g->R;
+  g->sOffB = g->sOffK + (int64_t)G * g->W * CONV_KC;
+  g->slab = (g->sOffB + g->N + 3) & ~(int64_t)3;
+  g->XP = (CONV_TT + g->W - 1) | 1;
+  const int fixed = DZ_FLOATS + CONV_TT * QP;
+  int dc = (LDS_BUDGET_FLOATS - fixed) / g->XP;
+  if (dc > g->D) dc = g->D;
+  if (dc >= 4) dc &= ~3;  // phase B deals columns to four waves
+  g->DC = dc;
+  g->lds_bytes = (size_t)(fixed + dc * g->XP) * 4;
+  return true;
+}
+
+void conv_build_maps(const ConvGeom& g, int32_t* kmap, int32_t* gmap) {
+  for (int64_t i = 0; i < (int64_t)g.G * g.W * CONV_KC; ++i) kmap[i] = -1;
+  for (int64_t e = 0; e < g.offKn; ++e) gmap[e] = (int32_t)e;  // Bd, Bo: same place in arena and slab
+  for (int n = 0; n < g.N; ++n) gmap[g.offB + n] = (int32_t)(g.sOffB + n);
+  for (int gi = 0; gi < g.G; ++gi) {
+    const ConvGroup& gr = g.grp[gi];
+    for (int j = 0; j < gr.nr; ++j) {
+      const int r = gr.rbase + j;
+      for (int c = 0; c < gr.cc; ++c)
+        for (int w = 0; w < g.W; ++w) {
+          const int64_t arena = r < g.Rn ? g.offKn + (int64_t)w * g.Rn + r
+                                         : g.offKs + ((int64_t)w * g.Rs + (r - g.Rn)) * g.C + c;
+          const int64_t pos = ((int64_t)gi * g.W + w) * CONV_KC + j * gr.cc + c;
+          kmap[pos] = (int32_t)arena;
+          gmap[arena] = (int32_t)(g.sOffK + pos);
+        }
+    }
+  }
+}
+
+hipError_t conv_prepare(const ConvGeom& g) {
+  // the attribute is per kernel, not per plan: always the whole budget (every plan's lds_bytes is within it)
+  if (g.lds_bytes > (size_t)LDS_BUDGET_FLOATS * 4) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv<1>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET_FLOATS * 4);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             LDS_BUDGET_FLOATS * 4);
+}
+
+hipError_t launch_conv_kp(const ConvGeom& g, const float* phi, const int32_t* kmap, float* Kp, const int32_t* stop,
+                          hipStream_t st) {
+  const int n = g.G * g.W * CONV_KC;
+  hipLaunchKernelGGL(k_conv_kp, dim3((n + 255) / 256), dim3(256), 0, st, n, phi, kmap, Kp, stop);
+  return hipGetLastError();
+}
+
+hipError_t launch_conv(int train, const ConvGeom& g, int grid, const float* X, int64_t T, int64_t xld,
+                       const float* phi, const float* params, const float* Kp, const float* y, float scale,
+                       float* gpart, double* dpart, float* ebuf, float* yhat, const int32_t* stop, hipStream_t st) {
+  if (T < g.W || grid < 1) return hipErrorInvalidValue;
+  if (train)
+    hipLaunchKernelGGL(k_conv<1>, dim3(grid), dim3(CONV_TT), g.lds_bytes, st, g, X, T, xld, phi, params, Kp, y, scale,
+                       gpart, dpart, ebuf, yhat, stop);
+  else
+    hipLaunchKernelGGL(k_conv<0>, dim3(grid), dim3(CONV_TT), g.lds_bytes, st, g, X, T, xld, phi, params, Kp, y, scale,
+                       gpart, dpart, ebuf, yhat, stop);
+  return hipGetLastError();
+}
+
+hipError_t launch_conv_finish(const ConvGeom& g, int nslabs, const float* gpart, const double* dpart,
+                              const int32_t* gmap, const float* dphi, double loss_scale, float* grad_out,
+                              const int32_t* stop, hipStream_t st) {
+  const int64_t n = g.nparams + 1;
+  hipLaunchKernelGGL(k_conv_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g.nparams, g.offB, nslabs,
+                     g.slab, gpart, dpart, gmap, dphi, loss_scale, grad_out, stop);
+  return hipGetLastError();
+}
+
+hipError_t launch_update_conv(const FactorSet& fs, int n_bias, const float lam[4], float* params, const float* grad,
+                              const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
+                              float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st) {
+  if (fs.nf != 4) return hipErrorInvalidValue;
+  ConvLam l;
+  for (int i = 0; i < 4; ++i) l.v[i] = lam[i];
+  hipLaunchKernelGGL(k_update_conv, dim3(1), dim3(1024), 0, st, fs, n_bias, l, params, grad, ua, m, v, vmax,
+                     grad_total_out, loss_out, loss_hist, stop);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (ua.mode == 0 && loss_hist != nullptr && stop != nullptr && ua.iter > ua.patience && ua.tol > 0.0)
+    e = launch_converge(loss_hist, ua.hist_base, ua.iter, ua.patience, ua.tol, stop, st);
+  return e;
+}
+
+}  // namespace tr
