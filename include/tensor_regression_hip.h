@@ -347,8 +347,38 @@ int tr_plan_create_conv(tr_plan** out, int device, int64_t n_w, int64_t n_d, int
                         float softplus_beta, float softplus_threshold);
 
 /* The conv plan's L2 weights: lambdas[3] = (w, d, out) as fit_Adam's lambda_L2 (host array, n = 3).
- * TR_E_ARG on a NULL plan or a plan of another model. */
+ * Also taken by a conv phase plan (below).  TR_E_ARG on a NULL plan or a plan of another model. */
 int tr_plan_set_l2_weights(tr_plan* plan, const float* lambdas, int n);
+
+/*
+ * Phase-constrained spectral convolutional model plan (an addition within ABI 9: no existing
+ * prototype or struct changes; phase_constrained_spectral_convolutional_tensor_regression.
+ * CP_linear_regression, …py:1034-1181; model forward_model :696-744 with phase_shifter :959-1027).
+ * The conv plan above with two spectral components of which the second is derived: a spectral rank
+ * carries one kernel and its pair is that kernel with every frequency shifted by 90 degrees,
+ *   z0 = X * phi(Ks),  z1 = X * H phi(Ks),  u_s = sqrt(z0^2 + z1^2),
+ *   (H k)[n] = sum_m h[(n - m) mod W] k[m],  h[d] = (2 / W) sum_{j=1..(W-1)/2} sin(2 pi j d / W)
+ * (H acts after the softplus; h is computed in fp64 with the exact pi/2 and rounded once).
+ * Arguments as tr_plan_create_conv without n_complex.  Parameter arena:
+ *   Bd (n_d, R) | Bo (n_out, R) | Kn (n_w, Rn) | Ks (n_w, Rs) | bias (n_out),  R = Rn + Rs
+ * tr_plan_factor_offset(plan, f) gives f = 0..3 and the bias offset for f = 4.
+ * With such a plan tr_forward, tr_loss_grad, tr_plan_num_params and tr_plan_num_grads carry the conv
+ * plan's meaning; tr_finalize_grad / tr_adam_step (with the NaN stop) need tr_plan_set_l2_weights
+ * and tr_plan_set_smoothness first and record the reference's total (…py:1412)
+ *   loss + l[0] (||Kn|| + ||Ks||) + l[1] ||Bd|| + l[2] ||Bo|| + sum_{F in (Kn, Ks), F non-empty}
+ *   lambda_smooth * mean((Delta^q F)^2),
+ * Delta^q = q rounds of a first difference with one zero row before and after (W + q rows).
+ * Same TR_E_ARG / TR_E_UNSUPPORTED split as tr_plan_create_conv (with R <= 32 the pair columns
+ * Rn + 2 Rs never exceed 64).  tr_plan_describe reports path=conv-1pass-fmaf+phase.
+ */
+#define TR_MODEL_CONV_PHASE 4
+int tr_plan_create_conv_phase(tr_plan** out, int device, int64_t n_w, int64_t n_d, int64_t n_out, int rank_normal,
+                              int rank_spectral, int64_t max_series_rows, const int32_t* non_negative,
+                              float softplus_beta, float softplus_threshold);
+
+/* The conv phase plan's smoothness term: lambda_smooth and smooth_diff_order (0..8) of fit / fit_Adam.
+ * TR_E_ARG on a NULL plan, a plan of another model or a diff_order outside 0..8. */
+int tr_plan_set_smoothness(tr_plan* plan, float lambda_smooth, int diff_order);
 
 /*
  * Per-kernel device timing (measurement support; no reference counterpart).

@@ -586,6 +586,51 @@ class ConvPlan(Plan):
         check(rc, "tr_adam_step")
 
 
+class ConvPhasePlan(ConvPlan):
+    """`tr_plan` of the phase-constrained convolutional model (phase_constrained_spectral_convolutional_
+    tensor_regression.CP_linear_regression): the conv plan with two spectral components of which the
+    second is derived on the device, arena = Bd (D, R) | Bo (N, R) | Kn (W, Rn) | Ks (W, Rs) | bias (N).
+    `lambda_l2` of finalize_grad / adam_step is the length-3 sequence (w, d, out); the smoothness
+    term's `lambda_smooth` / `diff_order` are plan state next to it (set_smoothness)."""
+
+    def __init__(self, n_w, n_d, n_out, rank_normal, rank_spectral, max_rows, non_negative, softplus_kwargs,
+                 device, lambda_smooth=0.0, diff_order=2):
+        self.lib = _lib.load()
+        self.dev = device_index(device)
+        self.device_str = f"cuda:{self.dev}"
+        self.model = _lib.TR_MODEL_CONV_PHASE
+        self.dtype, self.f64, self._sfx = torch.float32, False, ""
+        self.dims = (int(n_w), int(n_d), int(n_out))
+        self.rank_normal, self.rank_spectral, self.n_complex = int(rank_normal), int(rank_spectral), 1
+        self.max_rows = int(max_rows)
+        self.n_factors = 4
+        self.nonlin = nonlin_key(non_negative, softplus_kwargs, 3)
+        nn = (ctypes.c_int32 * 3)(*self.nonlin[0])
+        beta, thr = self.nonlin[1:]
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.dev):
+            rc = self.lib.tr_plan_create_conv_phase(ctypes.byref(h), self.dev, self.dims[0], self.dims[1],
+                                                    self.dims[2], self.rank_normal, self.rank_spectral,
+                                                    max(1, self.max_rows), nn, beta, thr)
+        check(rc, "tr_plan_create_conv_phase")
+        self.h = h
+        _track(self)
+        self.num_params = int(self.lib.tr_plan_num_params(h))
+        self.num_grads = int(self.lib.tr_plan_num_grads(h))
+        self.offsets = [int(self.lib.tr_plan_factor_offset(h, f)) for f in range(5)]
+        self.describe = self.lib.tr_plan_describe(h).decode()
+        self._lam = None
+        self._smooth = None
+        self.set_smoothness(lambda_smooth, diff_order)
+
+    def set_smoothness(self, lambda_smooth, diff_order):
+        sm = (float(lambda_smooth), int(diff_order))
+        if sm != self._smooth:
+            check(self.lib.tr_plan_set_smoothness(self.h, sm[0], sm[1]), "tr_plan_set_smoothness")
+            self._smooth = sm
+        self.lambda_smooth, self.diff_order = sm
+
+
 def _rows_contiguous(X):
     """Each X[n] block is contiguous (any stride, even overlapping, along dim 0)."""
     expect = 1

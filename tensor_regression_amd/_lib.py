@@ -19,6 +19,7 @@ TR_MODEL_LINEAR = 0
 TR_MODEL_MULTINOMIAL = 1
 TR_MODEL_SPECTRAL = 2
 TR_MODEL_CONV_SPECTRAL = 3
+TR_MODEL_CONV_PHASE = 4
 TR_MAX_FACTORS = 8
 KERNEL_KINDS = ["stream_fused", "stream_rows", "stream_cols", "reduce", "mttkrp", "prep", "update"]
 
@@ -52,6 +53,9 @@ SIGNATURES = {
                                        _c.c_int, _c.c_int, _c.c_int64, _c.POINTER(_c.c_int32), _c.c_float,
                                        _c.c_float]),
     "tr_plan_set_l2_weights": (_c.c_int, [_vp, _c.POINTER(_c.c_float), _c.c_int]),
+    "tr_plan_create_conv_phase": (_c.c_int, [_c.POINTER(_vp), _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int,
+                                             _c.c_int, _c.c_int64, _c.POINTER(_c.c_int32), _c.c_float, _c.c_float]),
+    "tr_plan_set_smoothness": (_c.c_int, [_vp, _c.c_float, _c.c_int]),
     "tr_spectral_latents": (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _vp, _vp]),
     "tr_plan_set_x_stride": (_c.c_int, [_vp, _c.c_int64]),
     "tr_x_range": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _vp, _c.c_int, _vp]),

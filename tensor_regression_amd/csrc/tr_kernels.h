@@ -118,6 +118,9 @@ hipError_t launch_update(const FactorSet& fs, int n_bias, float* params, const f
 // the plateau test alone (fit_Adam's stop rule, standard…py:467-470) on the fp64 loss history
 hipError_t launch_converge(const double* loss_hist, int64_t hist_base, int64_t iter, int64_t patience, double tol,
                            int32_t* stop, hipStream_t st);
+// the plateau test over loss_running[-patience+1:] of n_losses entries (needs n_losses > patience)
+hipError_t launch_converge_tail(const double* loss_hist, int64_t n_losses, int64_t iter, int64_t patience, double tol,
+                                int32_t* stop, hipStream_t st);
 // whether k_update can prepare the next iteration in this mode for this factor set
 bool update_prepare_mode_ok(const FactorSet& fs, int mode);
 // MTTKRP of a two-factor model, one wave per factor row (tr_update.hip); launch_mttkrp uses it

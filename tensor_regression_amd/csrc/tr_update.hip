@@ -251,6 +251,26 @@ hipError_t launch_converge(const double* loss_hist, int64_t hist_base, int64_t i
   return hipGetLastError();
 }
 
+// The plateau test of the reference's later modules (phase_constrained…py:1445-1448): checked once
+// len(loss_running) > patience, over the slice loss_running[-patience+1:] (the whole list for
+// patience = 1, all but the first entry for patience = 0).  n_losses = len(loss_running).
+__global__ __launch_bounds__(64) void k_converge_tail(const double* __restrict__ loss_hist, int64_t n_losses,
+                                                      int64_t iter, int64_t patience, double tol,
+                                                      int32_t* __restrict__ stop) {
+  if (*stop != 0 || threadIdx.x != 0) return;
+  const int64_t s = patience >= 2 ? n_losses - (patience - 1) : 1 - patience;
+  const int64_t cnt = n_losses - 1 - s;  // number of diffs in the slice
+  const double d = cnt > 0 ? np_pairwise_sum_absdiff(loss_hist + s, cnt) : 0.0;
+  if (d < tol) *stop = (int32_t)(iter + 1);  // iterations completed in this fit
+}
+
+hipError_t launch_converge_tail(const double* loss_hist, int64_t n_losses, int64_t iter, int64_t patience, double tol,
+                                int32_t* stop, hipStream_t st) {
+  if (n_losses <= patience || patience < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_converge_tail, dim3(1), dim3(64), 0, st, loss_hist, n_losses, iter, patience, tol, stop);
+  return hipGetLastError();
+}
+
 // ==========================================================================================
 // MTTKRP of a two-factor model (config 2: rows 256 + 128, rank 8), one wave per factor row:
 //   grad[A_f][i, r] = dphi * sum_j G[i_f = i, i_g = j] * (w_r * Phi_g[j, r])      (g = 1 - f)
