@@ -4,7 +4,8 @@
 //   L2_penalty (standard…py:180-196): sum_k sqrt(sum(A_k^2)) over RAW factors (not squared)
 //   d/dA [lambda*sqrt(sum A^2)] = (lambda / (2 ||A||)) * (2 A)     (Sqrt/Pow backward)
 //   torch/optim/adam.py _single_tensor_adam (torch 2.10), non-capturable branch.
-//   numpy's pairwise summation is restated for np.sum(np.abs(np.diff(...))) (k_converge).
+//   numpy's summation (pairwise within chunks of 8192 elements) is restated for
+//   np.sum(np.abs(np.diff(...))) (k_converge).
 //
 // One 1024-thread workgroup: the norms are a dependency of every element, and several
 // workgroups could not overwrite a factor before all had read it.  The step is a few thousand
@@ -51,9 +52,10 @@ __device__ __forceinline__ int factor_of(const FactorSet& fs, int64_t e) {
 }
 }
 
-__device__ double np_pairwise_sum_absdiff(const double* h, int64_t n) {
-  // sum_{j<n} |h[j+1] - h[j]| in numpy's pairwise order (PW_BLOCKSIZE 128, 8 accumulators),
-  // iterative over the recursion tree (left-first), n <= 2^20.
+namespace {
+// sum_{j<n} |h[j+1] - h[j]| in the order of numpy's DOUBLE_pairwise_sum (PW_BLOCKSIZE 128, 8
+// accumulators), iterative over the recursion tree (left-first), n <= NP_BUFSIZE.
+__device__ double np_pairwise_block_absdiff(const double* h, int64_t n) {
   double total = 0.0;
   // explicit stack of (start, len, depth-combine) — emulate recursion with partial sums
   struct Frame { int64_t s, n; int state; double left; };
@@ -98,6 +100,18 @@ __device__ double np_pairwise_sum_absdiff(const double* h, int64_t n) {
     }
   }
   total = ret;
+  return total;
+}
+constexpr int64_t NP_BUFSIZE = 8192;  // numpy's ufunc buffer, in elements (np.getbufsize() default)
+}  // namespace
+
+// np.sum(np.abs(np.diff(h[0 : n + 1]))) as numpy adds it up: the reduction takes its operand in
+// chunks of NP_BUFSIZE elements, sums each chunk pairwise and adds the chunk sums to the running
+// result one after another (up to 8192 terms: one pairwise sum).
+__device__ double np_pairwise_sum_absdiff(const double* h, int64_t n) {
+  double total = -0.0;  // the identity numpy's add reduction starts from
+  for (int64_t c = 0; c < n; c += NP_BUFSIZE)
+    total += np_pairwise_block_absdiff(h + c, n - c < NP_BUFSIZE ? n - c : NP_BUFSIZE);
   return total;
 }
 

@@ -118,6 +118,28 @@ def test_plateau_sum_order_matches_numpy(seed):
         assert _pairwise(list(d)) == np.sum(d)
 
 
+def _chunked_pairwise(a, buf=8192):
+    """np.sum above its buffer of 8192 elements: one pairwise sum per chunk, the chunk sums added one after
+    another (np_pairwise_sum_absdiff's outer loop)."""
+    tot = -0.0
+    for c in range(0, len(a), buf):
+        tot += _pairwise(a[c:c + buf])
+    return tot
+
+
+@pytest.mark.parametrize("n", [8192, 8193, 8200, 16385, 20000])
+def test_plateau_sum_is_chunked_above_numpy_buffer(n):
+    """Beyond 8192 terms np.sum is not one pairwise sum: at least one of the seeds tells the two apart."""
+    assert np.getbufsize() == 8192
+    apart = 0
+    for seed in range(6):
+        rng = np.random.default_rng(seed)
+        d = np.abs(np.diff(rng.standard_normal(n + 1) * 10 ** rng.uniform(-6, 2)))
+        assert _chunked_pairwise(list(d)) == np.sum(d)
+        apart += _pairwise(list(d)) != np.sum(d)
+    assert (apart > 0) == (n > 8192)
+
+
 def test_model_constructors_cpu_only():
     """Construction and init (RNG-identical to the reference) need no GPU."""
     import torch
