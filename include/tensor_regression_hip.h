@@ -347,7 +347,8 @@ int tr_plan_create_conv(tr_plan** out, int device, int64_t n_w, int64_t n_d, int
                         float softplus_beta, float softplus_threshold);
 
 /* The conv plan's L2 weights: lambdas[3] = (w, d, out) as fit_Adam's lambda_L2 (host array, n = 3).
- * Also taken by a conv phase plan (below).  TR_E_ARG on a NULL plan or a plan of another model. */
+ * Also taken by a conv phase plan and a conv Fourier plan (below).  TR_E_ARG on a NULL plan or a plan
+ * of another model. */
 int tr_plan_set_l2_weights(tr_plan* plan, const float* lambdas, int n);
 
 /*
@@ -377,8 +378,57 @@ int tr_plan_create_conv_phase(tr_plan** out, int device, int64_t n_w, int64_t n_
                               float softplus_beta, float softplus_threshold);
 
 /* The conv phase plan's smoothness term: lambda_smooth and smooth_diff_order (0..8) of fit / fit_Adam.
- * TR_E_ARG on a NULL plan, a plan of another model or a diff_order outside 0..8. */
+ * Also taken by a conv Fourier plan (below).  TR_E_ARG on a NULL plan, a plan of another model or a
+ * diff_order outside 0..8. */
 int tr_plan_set_smoothness(tr_plan* plan, float lambda_smooth, int diff_order);
+
+/*
+ * Convolutional Fourier model plan (an addition within ABI 9: no existing prototype or struct
+ * changes; convolutional_fourier_tensor_regression.CP_linear_regression, …py:909-1050; model
+ * forward_model :694-725).  The conv plan's model (unconstrained Ks (n_w, Rs, n_complex), magnitude
+ * over the components) with the phase plan's smoothness term and the output-spectrum penalty.
+ * Arguments, parameter arena, TR_E_ARG / TR_E_UNSUPPORTED split and envelope are those of
+ * tr_plan_create_conv.  tr_plan_set_l2_weights and tr_plan_set_smoothness accept the plan and are
+ * both required before tr_finalize_grad / tr_adam_step, which record the reference's total (:1281)
+ *   ((((loss_rec + L2_w) + L2_n) + loss_spectral) + loss_smoothness),
+ * the smoothness term over Kn and Ks with Ks seen as (n_w, Rs * n_complex); stops as a phase plan.
+ * tr_plan_describe reports path=conv-1pass-fmaf+fourier, and +spectrum-dft while the penalty is on.
+ */
+#define TR_MODEL_CONV_FOURIER 5
+int tr_plan_create_conv_fourier(tr_plan** out, int device, int64_t n_w, int64_t n_d, int64_t n_out, int rank_normal,
+                                int rank_spectral, int n_complex, int64_t max_series_rows,
+                                const int32_t* non_negative, float softplus_beta, float softplus_threshold);
+
+/*
+ * The output-spectrum penalty of a conv Fourier plan (spectral_penalty, …py:727-812):
+ *   Y = rfft(y_hat, n_fft) (y_hat zero-padded from T' rows), A = |Y| (F = n_fft / 2 + 1 bins),
+ *   M[j] = sum_{s < n_kernel} A[j + s] g[s] (Fs = F - n_kernel + 1 rows), M_y the same of the target,
+ *   pen = lambda * mean(((M - M_y) / (M_y + 1e-8))^2).
+ * The transform is a direct real DFT of any length with exact integer angle indices (twiddles from an
+ * n_fft-entry table computed in fp64); every sum has one fixed order.
+ *   kernel_host   host float[n_kernel]: g; n_kernel = 0 turns the penalty off (the other arguments
+ *                 are then ignored); n_kernel <= 4097
+ *   n_fft         transform length, 1 <= n_fft <= 2^22
+ *   target_dev    device (n_rows x n_out) series whose smoothed spectrum M_y is computed here (on
+ *                 `stream`) and kept
+ * Sizes the spectrum workspace (counted by tr_plan_workspace_bytes).  While the penalty is on,
+ * tr_loss_grad runs k_conv forward -> DFT -> spectrum terms -> adjoint DFT -> k_conv with the
+ * penalty's gradient added to the residual; its loss slot keeps loss_rec alone, the penalty value
+ * stays in a plan-owned device scalar that the update step adds, and n_rows - n_w + 1 <= n_fft is
+ * required.  TR_E_ARG on a NULL plan, a plan of another model, n_rows > n_fft, n_rows < 1,
+ * n_fft / 2 + 1 < n_kernel, or NULL pointers with n_kernel > 0.
+ */
+int tr_plan_set_spectrum_penalty(tr_plan* plan, float lambda, const float* kernel_host, int n_kernel, int64_t n_fft,
+                                 const float* target_dev, int64_t n_rows, void* stream);
+
+/* The smoothed magnitude spectrum M (Fs x n_out) of a device series (n_rows x n_out, n_rows <= n_fft)
+ * with the plan's g and n_fft.  TR_E_ARG without tr_plan_set_spectrum_penalty (n_kernel > 0) first. */
+int tr_conv_spectrum(tr_plan* plan, const float* series_dev, int64_t n_rows, float* out_dev, void* stream);
+
+/* The penalty value (one float) and d pen / d series (n_rows x n_out) of a device series: the stages
+ * tr_loss_grad runs between its two X passes. */
+int tr_conv_spectrum_penalty(tr_plan* plan, const float* series_dev, int64_t n_rows, float* value_out_dev,
+                             float* grad_out_dev, void* stream);
 
 /*
  * Per-kernel device timing (measurement support; no reference counterpart).

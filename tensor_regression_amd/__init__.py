@@ -10,6 +10,7 @@ from . import _lib  # noqa: F401
 from . import standard_tensor_regression  # noqa: F401
 from . import multinomial_tensor_regression  # noqa: F401
 from . import spectral_tensor_regression  # noqa: F401
+from . import convolutional_fourier_tensor_regression  # noqa: F401
 from .standard_tensor_regression import CP_linear_regression  # noqa: F401
 from .multinomial_tensor_regression import CP_logistic_regression  # noqa: F401
 

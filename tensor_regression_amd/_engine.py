@@ -631,6 +631,84 @@ class ConvPhasePlan(ConvPlan):
         self.lambda_smooth, self.diff_order = sm
 
 
+class ConvFourierPlan(ConvPlan):
+    """`tr_plan` of the convolutional Fourier model (convolutional_fourier_tensor_regression.
+    CP_linear_regression): the conv plan's arena and X pass, the phase plan's smoothness term
+    (set_smoothness) and the output-spectrum penalty (set_spectrum_penalty), both plan state."""
+
+    def __init__(self, n_w, n_d, n_out, rank_normal, rank_spectral, n_complex, max_rows, non_negative,
+                 softplus_kwargs, device, lambda_smooth=0.0, diff_order=2):
+        self.lib = _lib.load()
+        self.dev = device_index(device)
+        self.device_str = f"cuda:{self.dev}"
+        self.model = _lib.TR_MODEL_CONV_FOURIER
+        self.dtype, self.f64, self._sfx = torch.float32, False, ""
+        self.dims = (int(n_w), int(n_d), int(n_out))
+        self.rank_normal, self.rank_spectral, self.n_complex = int(rank_normal), int(rank_spectral), int(n_complex)
+        self.max_rows = int(max_rows)
+        self.n_factors = 4
+        self.nonlin = nonlin_key(non_negative, softplus_kwargs, 3)
+        nn = (ctypes.c_int32 * 3)(*self.nonlin[0])
+        beta, thr = self.nonlin[1:]
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.dev):
+            rc = self.lib.tr_plan_create_conv_fourier(ctypes.byref(h), self.dev, self.dims[0], self.dims[1],
+                                                      self.dims[2], self.rank_normal, self.rank_spectral,
+                                                      self.n_complex, max(1, self.max_rows), nn, beta, thr)
+        check(rc, "tr_plan_create_conv_fourier")
+        self.h = h
+        _track(self)
+        self.num_params = int(self.lib.tr_plan_num_params(h))
+        self.num_grads = int(self.lib.tr_plan_num_grads(h))
+        self.offsets = [int(self.lib.tr_plan_factor_offset(h, f)) for f in range(5)]
+        self.describe = self.lib.tr_plan_describe(h).decode()
+        self._lam = None
+        self._smooth = None
+        self.spectrum = None  # (n_fft, n_kernel) while the penalty is on
+        self.set_smoothness(lambda_smooth, diff_order)
+
+    set_smoothness = ConvPhasePlan.set_smoothness
+
+    def set_spectrum_penalty(self, lam, kernel, n_fft, target):
+        """lam, the smoothing kernel (1-D, host), n_fft and the (rows, n_out) device series whose smoothed
+        spectrum becomes M_y; kernel=None turns the penalty off.  Returns M_y's shape (Fs, n_out) or None."""
+        if kernel is None:
+            check(self.lib.tr_plan_set_spectrum_penalty(self.h, 0.0, None, 0, 0, None, 0, None),
+                  "tr_plan_set_spectrum_penalty")
+            self.spectrum = None
+        else:
+            g = np.ascontiguousarray(np.asarray(kernel, dtype=np.float32).reshape(-1))
+            arr = g.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+            with torch.cuda.device(self.dev):
+                rc = self.lib.tr_plan_set_spectrum_penalty(self.h, float(lam), arr, int(g.size), int(n_fft),
+                                                           ptr(target), int(target.shape[0]),
+                                                           stream_handle(self.dev))
+            check(rc, "tr_plan_set_spectrum_penalty")
+            self.spectrum = (int(n_fft), int(g.size))
+        self.describe = self.lib.tr_plan_describe(self.h).decode()
+        return None if self.spectrum is None else (int(n_fft) // 2 + 1 - self.spectrum[1] + 1, self.dims[2])
+
+    def conv_spectrum(self, series, out=None):
+        """Smoothed magnitude spectrum M (Fs, n_out) of a (rows, n_out) fp32 device series."""
+        if self.spectrum is None:
+            raise ValueError("conv_spectrum: call set_spectrum_penalty first")
+        n_fft, S = self.spectrum
+        if out is None:
+            out = torch.empty((n_fft // 2 + 1 - S + 1, self.dims[2]), dtype=torch.float32, device=series.device)
+        rc = self.lib.tr_conv_spectrum(self.h, ptr(series), int(series.shape[0]), ptr(out), stream_handle(self.dev))
+        check(rc, "tr_conv_spectrum")
+        return out
+
+    def conv_spectrum_penalty(self, series):
+        """(value (1,), d pen / d series (rows, n_out)) of a (rows, n_out) fp32 device series."""
+        value = torch.empty(1, dtype=torch.float32, device=series.device)
+        grad = torch.empty_like(series)
+        rc = self.lib.tr_conv_spectrum_penalty(self.h, ptr(series), int(series.shape[0]), ptr(value), ptr(grad),
+                                               stream_handle(self.dev))
+        check(rc, "tr_conv_spectrum_penalty")
+        return value, grad
+
+
 def _rows_contiguous(X):
     """Each X[n] block is contiguous (any stride, even overlapping, along dim 0)."""
     expect = 1

@@ -20,6 +20,7 @@ TR_MODEL_MULTINOMIAL = 1
 TR_MODEL_SPECTRAL = 2
 TR_MODEL_CONV_SPECTRAL = 3
 TR_MODEL_CONV_PHASE = 4
+TR_MODEL_CONV_FOURIER = 5
 TR_MAX_FACTORS = 8
 KERNEL_KINDS = ["stream_fused", "stream_rows", "stream_cols", "reduce", "mttkrp", "prep", "update"]
 
@@ -56,6 +57,13 @@ SIGNATURES = {
     "tr_plan_create_conv_phase": (_c.c_int, [_c.POINTER(_vp), _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int,
                                              _c.c_int, _c.c_int64, _c.POINTER(_c.c_int32), _c.c_float, _c.c_float]),
     "tr_plan_set_smoothness": (_c.c_int, [_vp, _c.c_float, _c.c_int]),
+    "tr_plan_create_conv_fourier": (_c.c_int, [_c.POINTER(_vp), _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64,
+                                               _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.POINTER(_c.c_int32),
+                                               _c.c_float, _c.c_float]),
+    "tr_plan_set_spectrum_penalty": (_c.c_int, [_vp, _c.c_float, _c.POINTER(_c.c_float), _c.c_int, _c.c_int64, _vp,
+                                                _c.c_int64, _vp]),
+    "tr_conv_spectrum": (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _vp]),
+    "tr_conv_spectrum_penalty": (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _vp, _vp]),
     "tr_spectral_latents": (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _vp, _vp]),
     "tr_plan_set_x_stride": (_c.c_int, [_vp, _c.c_int64]),
     "tr_x_range": (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _vp, _c.c_int, _vp]),

@@ -52,10 +52,12 @@ hipError_t conv_prepare(const ConvGeom& g);
 // softplus'd factors -> padded kernel columns Kp (G, W, 16)
 hipError_t launch_conv_kp(const ConvGeom& g, const float* phi, const int32_t* kmap, float* Kp, const int32_t* stop,
                           hipStream_t st);
-// train = 1: forward + loss + all gradients into the workgroups' slabs; train = 0: y_hat only
+// train = 1: forward + loss + all gradients into the workgroups' slabs; train = 0: y_hat only.
+// eadd (T', N), nullable: added to the residual scale * (y_hat - y) before the backward phases
 hipError_t launch_conv(int train, const ConvGeom& g, int grid, const float* X, int64_t T, int64_t xld,
                        const float* phi, const float* params, const float* Kp, const float* y, float scale,
-                       float* gpart, double* dpart, float* ebuf, float* yhat, const int32_t* stop, hipStream_t st);
+                       float* gpart, double* dpart, float* ebuf, const float* eadd, float* yhat, const int32_t* stop,
+                       hipStream_t st);
 // fixed-order slab sum + softplus chain + loss slot + status slot
 hipError_t launch_conv_finish(const ConvGeom& g, int nslabs, const float* gpart, const double* dpart,
                               const int32_t* gmap, const float* dphi, double loss_scale, float* grad_out,

@@ -14,7 +14,8 @@
 //   phase A   thread = one output time, its columns serial: z for one group of 16 kernel columns
 //             at a time (16 accumulators; the kernel row Kp[g][w][0..15] is wave-uniform), then
 //             u and q.  q stays thread-private (LDS row of the thread): no cross-lane reduction.
-//   epilogue  y_hat, squared error (double), e = 2 (y_hat - y) / (T' N) to a global scratch,
+//   epilogue  y_hat, squared error (double), e = 2 (y_hat - y) / (T' N) (+ eadd[t, n] when a penalty on
+//             y_hat brings its own gradient: tr_conv_spectrum.hip) to a global scratch,
 //             dBo / dbias by one thread per entry over the tile's times, dq = e . Bo in place of q.
 //   phase B   wave = every fourth column of the chunk, its lanes the times of one 64-time
 //             subtile after another: z recomputed from the slab still in LDS, dBd by one wave
@@ -25,7 +26,7 @@
 // Every workgroup adds into its own gradient slab (same thread, same order every time);
 // k_conv_finish sums the slabs in index order and applies the softplus chain.  No float atomics:
 // two runs on the same inputs are bitwise equal.
-// k_conv<0> is phase A + y_hat only (predict).
+// k_conv<0> is phase A + y_hat only (predict); k_conv<2> is k_conv<1> with eadd.
 //
 // Form: fp32 fmaf on the VALU throughout ("conv-1pass-fmaf").  Bounds: every LDS index is
 // < DC*XP + 256*QP + 4*64*16 (conv_geom_init sizes the allocation from the same terms); slab rows
@@ -210,7 +211,8 @@ __global__ __launch_bounds__(CONV_TT) void k_conv(ConvGeom g, const float* __res
                                                   const float* __restrict__ Kp, const float* __restrict__ y,
                                                   float scale, float* gpart, double* __restrict__ dpart,
                                                   float* ebuf, float* __restrict__ yhat,
-                                                  const int32_t* __restrict__ stop) {
+                                                  const int32_t* __restrict__ stop,
+                                                  const float* __restrict__ eadd) {
   if (stop != nullptr && *stop != 0) return;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int XP = g.XP, W = g.W, R = g.R, N = g.N, D = g.D, DC = g.DC;
@@ -270,7 +272,10 @@ __global__ __launch_bounds__(CONV_TT) void k_conv(ConvGeom g, const float* __res
         if (TRAIN) {
           const float diff = yh - y[t * N + n];
           lossacc += (double)diff * (double)diff;
-          ebuf[t * N + n] = scale * diff;
+          // TRAIN == 2: eadd, the gradient of a penalty on y_hat (the spectrum penalty), joins the
+          // residual's; an instantiation of its own and the last kernel argument, so that k_conv<1>
+          // and k_conv<0> stay the code they were
+          ebuf[t * N + n] = TRAIN == 2 ? scale * diff + eadd[t * N + n] : scale * diff;
         }
       }
     }
@@ -543,6 +548,9 @@ hipError_t conv_prepare(const ConvGeom& g) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv<1>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BUDGET_FLOATS * 4);
   if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          LDS_BUDGET_FLOATS * 4);
+  if (e != hipSuccess) return e;
   return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              LDS_BUDGET_FLOATS * 4);
 }
@@ -556,14 +564,18 @@ hipError_t launch_conv_kp(const ConvGeom& g, const float* phi, const int32_t* km
 
 hipError_t launch_conv(int train, const ConvGeom& g, int grid, const float* X, int64_t T, int64_t xld,
                        const float* phi, const float* params, const float* Kp, const float* y, float scale,
-                       float* gpart, double* dpart, float* ebuf, float* yhat, const int32_t* stop, hipStream_t st) {
+                       float* gpart, double* dpart, float* ebuf, const float* eadd, float* yhat, const int32_t* stop,
+                       hipStream_t st) {
   if (T < g.W || grid < 1) return hipErrorInvalidValue;
-  if (train)
+  if (train && eadd != nullptr)
+    hipLaunchKernelGGL(k_conv<2>, dim3(grid), dim3(CONV_TT), g.lds_bytes, st, g, X, T, xld, phi, params, Kp, y, scale,
+                       gpart, dpart, ebuf, yhat, stop, eadd);
+  else if (train)
     hipLaunchKernelGGL(k_conv<1>, dim3(grid), dim3(CONV_TT), g.lds_bytes, st, g, X, T, xld, phi, params, Kp, y, scale,
-                       gpart, dpart, ebuf, yhat, stop);
+                       gpart, dpart, ebuf, yhat, stop, eadd);
   else
     hipLaunchKernelGGL(k_conv<0>, dim3(grid), dim3(CONV_TT), g.lds_bytes, st, g, X, T, xld, phi, params, Kp, y, scale,
-                       gpart, dpart, ebuf, yhat, stop);
+                       gpart, dpart, ebuf, yhat, stop, eadd);
   return hipGetLastError();
 }
 

@@ -1,0 +1,489 @@
+// tr_conv_spectrum.hip — the output-spectrum penalty of the convolutional Fourier model
+// (convolutional_fourier_tensor_regression.py: spectral_penalty 727-812, set up at 1040-1048 and
+// 1260-1261; loss 1269-1282) and that model's update step.
+//
+//   C[k,n] = sum_{t<rows} x[t,n] cos(2 pi k t / n_fft),  S[k,n] = sum_t x[t,n] sin(2 pi k t / n_fft)
+//            (Y = rfft(x, n_fft) = C - i S; the series is zero-padded from rows to n_fft)     k < F
+//   A      = |Y|
+//   M[j,n] = sum_{s<S} A[j+s,n] g[s]                                                         j < Fs
+//   pen    = lambda_sp mean_{j,n} ((M - M_y) / (M_y + 1e-8))^2
+// and back:
+//   dM[j,n] = 2 lambda_sp / (Fs N) (M - M_y) / (M_y + 1e-8)^2
+//   dA[k,n] = sum_s dM[k-s,n] g[s]                       (0 <= k - s < Fs)
+//   d pen / d x[t,n] = sum_{k<F} (dA / A)[k,n] (C[k,n] cos(2 pi k t / n_fft) + S[k,n] sin(2 pi k t / n_fft))
+//            (torch's abs backward: 0 where A = 0; the F bins only, no factor 2 for the mirrored half)
+//
+//   k_dft<ADJ>   out[a,n] = sum_b in[b,n] {cos, sin}(2 pi a b / n_fft): one thread owns one output
+//                index a and NC = 4 columns; the summation index b runs over tiles of 256 rows staged
+//                in LDS (every lane reads the same row: broadcast).  The angle index (a b) mod n_fft
+//                is exact: a 64-bit product once per (thread, split), then add-and-wrap by
+//                (a RUN) mod n_fft per run of RUN = 8 terms.  Each run is seeded from the table
+//                tw[i] = (cos, sin)(2 pi i / n_fft) (fp64 on the host, rounded once) and bridged by
+//                the rotation by tw[a]: at most 7 rotations from an exact seed.  fp32 fmaf inside a
+//                tile, the tiles' sums accumulated in fp64.  The b range is split over blockIdx.z
+//                when a and n alone give too few workgroups; the splits' fp64 partials are added in
+//                index order by k_dft_combine.  ADJ = 0: real in, C and S out; ADJ = 1: two ins, one out.
+//   k_spec_smooth / k_spec_pen / k_spec_val / k_spec_back   the terms between the two DFT passes, one
+//                thread per element, every sum in ascending index order; the mean's partials are fp64
+//                (one per workgroup, added in index order), the value is fp32(mean) * lambda_sp.
+//   k_update_conv_fourier   k_update_conv_phase (tr_conv_phase.hip) restated for this model: the
+//                smoothness term over [Kn | Ks] with Ks seen as (W, Rs C) (up to (257 + 8) x 64: dynamic
+//                LDS), total = (((rec + L2_w) + L2_n) + spec) + smooth, stops through k_converge_tail.
+// No float atomics; two runs on the same inputs are bitwise equal.  Every kernel returns at once when
+// the device stop flag is set.
+// Bounds: a thread with a >= A computes index 0 and stores nothing; tile rows >= the split's end are
+// zero; every table index is < n_fft (a < A <= n_fft, wrapped sums < 2 n_fft <= 2^23).
+#include <cmath>
+#include <cstring>
+
+#include "tr_conv_spectrum.h"
+
+namespace tr {
+
+namespace {
+constexpr int DFT_T = 256;   // threads of a workgroup = output indices
+constexpr int DFT_BT = 256;  // summation indices per LDS tile
+constexpr int DFT_NC = 4;    // columns per workgroup
+constexpr int DFT_RUN = 8;   // terms per exact re-seed of the twiddle
+constexpr int PEN_EPB = 1024;  // elements per workgroup of k_spec_pen
+}  // namespace
+
+template <int ADJ>
+__global__ __launch_bounds__(DFT_T) void k_dft(int64_t A, int64_t B, int N, uint32_t nfft, int64_t bper,
+                                               const float2* __restrict__ tw, const float* __restrict__ in0,
+                                               const float* __restrict__ in1, double* __restrict__ part,
+                                               const int32_t* __restrict__ stop) {
+  if (stop != nullptr && *stop != 0) return;
+  __shared__ float4 s0[DFT_BT];
+  __shared__ float4 s1[ADJ ? DFT_BT : 1];
+  const int tid = threadIdx.x;
+  const int64_t a = (int64_t)blockIdx.x * DFT_T + tid;
+  const int n0 = blockIdx.y * DFT_NC;
+  const int64_t b_begin = (int64_t)blockIdx.z * bper;
+  const int64_t b_end = b_begin + bper < B ? b_begin + bper : B;
+  const uint64_t ac = a < A ? (uint64_t)a : 0;
+  const uint32_t step = (uint32_t)((ac * DFT_RUN) % nfft);
+  uint32_t idx = (uint32_t)((ac * (uint64_t)b_begin) % nfft);
+  const float2 w = tw[ac];
+  double acc0[DFT_NC], acc1[DFT_NC];
+#pragma unroll
+  for (int i = 0; i < DFT_NC; ++i) acc0[i] = acc1[i] = 0.0;
+  for (int64_t b0 = b_begin; b0 < b_end; b0 += DFT_BT) {
+    __syncthreads();  // the tile's previous readers are done
+    {
+      const int64_t b = b0 + tid;
+      float v0[DFT_NC], v1[DFT_NC];
+#pragma unroll
+      for (int i = 0; i < DFT_NC; ++i) {
+        const bool ok = b < b_end && n0 + i < N;
+        v0[i] = ok ? in0[b * N + n0 + i] : 0.f;
+        v1[i] = ADJ && ok ? in1[b * N + n0 + i] : 0.f;
+      }
+      s0[tid] = make_float4(v0[0], v0[1], v0[2], v0[3]);
+      if (ADJ) s1[tid] = make_float4(v1[0], v1[1], v1[2], v1[3]);
+    }
+    __syncthreads();
+    float f0[DFT_NC], f1[DFT_NC];
+#pragma unroll
+    for (int i = 0; i < DFT_NC; ++i) f0[i] = f1[i] = 0.f;
+    for (int j = 0; j < DFT_BT; j += DFT_RUN) {
+      float2 cs = tw[idx];
+      idx += step;
+      if (idx >= nfft) idx -= nfft;
+#pragma unroll
+      for (int r = 0; r < DFT_RUN; ++r) {
+        const float4 x4 = s0[j + r];
+        const float x[DFT_NC] = {x4.x, x4.y, x4.z, x4.w};
+        if (ADJ) {
+          const float4 y4 = s1[j + r];
+          const float y[DFT_NC] = {y4.x, y4.y, y4.z, y4.w};
+#pragma unroll
+          for (int i = 0; i < DFT_NC; ++i) f0[i] = fmaf(y[i], cs.y, fmaf(x[i], cs.x, f0[i]));
+        } else {
+#pragma unroll
+          for (int i = 0; i < DFT_NC; ++i) {
+            f0[i] = fmaf(x[i], cs.x, f0[i]);
+            f1[i] = fmaf(x[i], cs.y, f1[i]);
+          }
+        }
+        if (r + 1 < DFT_RUN) {  // angle + 2 pi a / n_fft
+          const float c = fmaf(cs.x, w.x, -(cs.y * w.y));
+          const float s = fmaf(cs.y, w.x, cs.x * w.y);
+          cs = make_float2(c, s);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < DFT_NC; ++i) {
+      acc0[i] += (double)f0[i];
+      acc1[i] += (double)f1[i];
+    }
+  }
+  if (a >= A) return;
+  const int nout = ADJ ? 1 : 2;
+  double* p0 = part + (((int64_t)blockIdx.z * nout) * A + a) * N;
+#pragma unroll
+  for (int i = 0; i < DFT_NC; ++i) {
+    if (n0 + i < N) {
+      p0[n0 + i] = acc0[i];
+      if (!ADJ) p0[A * N + n0 + i] = acc1[i];
+    }
+  }
+}
+
+// out[e] = sum over the splits, in index order; MAG: also |out0 + i out1| from the fp64 sums
+template <int MAG>
+__global__ __launch_bounds__(256) void k_dft_combine(int nsplit, int64_t AN, const double* __restrict__ part,
+                                                     float* __restrict__ out0, float* __restrict__ out1,
+                                                     float* __restrict__ mag, const int32_t* __restrict__ stop) {
+  if (stop != nullptr && *stop != 0) return;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= AN) return;
+  const int nout = MAG ? 2 : 1;
+  double s0 = 0.0, s1 = 0.0;
+  for (int z = 0; z < nsplit; ++z) {
+    s0 += part[((int64_t)z * nout) * AN + e];
+    if (MAG) s1 += part[((int64_t)z * nout + 1) * AN + e];
+  }
+  out0[e] = (float)s0;
+  if (MAG) {
+    out1[e] = (float)s1;
+    mag[e] = (float)sqrt(s0 * s0 + s1 * s1);
+  }
+}
+
+// M[j,n] = sum_s A[j+s,n] g[s]   (conv1d: no flip)
+__global__ __launch_bounds__(256) void k_spec_smooth(int64_t FsN, int N, int S, const float* __restrict__ A,
+                                                     const float* __restrict__ g, float* __restrict__ M,
+                                                     const int32_t* __restrict__ stop) {
+  if (stop != nullptr && *stop != 0) return;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= FsN) return;
+  const float* a = A + e;  // A[(j + s) N + n] = A[e + s N]
+  float m = 0.f;
+  for (int s = 0; s < S; ++s) m = fmaf(a[(int64_t)s * N], g[s], m);
+  M[e] = m;
+}
+
+// dM and the workgroup's partial sum of ((M - My) / (My + 1e-8))^2
+__global__ __launch_bounds__(256) void k_spec_pen(int64_t FsN, float coef, const float* __restrict__ M,
+                                                  const float* __restrict__ My, float* __restrict__ dM,
+                                                  double* __restrict__ ppart, const int32_t* __restrict__ stop) {
+  if (stop != nullptr && *stop != 0) return;
+  __shared__ double wl[4];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int i = 0; i < PEN_EPB / 256; ++i) {
+    const int64_t e = (int64_t)blockIdx.x * PEN_EPB + i * 256 + tid;
+    if (e < FsN) {
+      const float den = My[e] + 1e-8f;
+      const float r = (M[e] - My[e]) / den;
+      acc += (double)r * (double)r;
+      dM[e] = coef * (r / den);
+    }
+  }
+  const double s = tr_wave_allreduce_d(acc);
+  if ((tid & 63) == 0) wl[tid >> 6] = s;
+  __syncthreads();
+  if (tid == 0) ppart[blockIdx.x] = (wl[0] + wl[1]) + (wl[2] + wl[3]);
+}
+
+// val = fp32(mean) * lambda_sp   (torch.mean(...) * lam)
+__global__ __launch_bounds__(64) void k_spec_val(int nb, double count, float lam, const double* __restrict__ ppart,
+                                                 float* __restrict__ val, const int32_t* __restrict__ stop) {
+  if (stop != nullptr && *stop != 0) return;
+  if (threadIdx.x != 0) return;
+  double s = 0.0;
+  for (int b = 0; b < nb; ++b) s += ppart[b];
+  *val = (float)(s / count) * lam;
+}
+
+// dA[k,n] = sum_s dM[k-s,n] g[s]; (re, im) *= dA / A  (0 where A = 0)
+__global__ __launch_bounds__(256) void k_spec_back(int64_t F, int64_t Fs, int N, int S, const float* __restrict__ dM,
+                                                   const float* __restrict__ g, const float* __restrict__ A,
+                                                   float* __restrict__ re, float* __restrict__ im,
+                                                   const int32_t* __restrict__ stop) {
+  if (stop != nullptr && *stop != 0) return;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= F * N) return;
+  const int64_t k = e / N;
+  const int64_t slo = k - Fs + 1 > 0 ? k - Fs + 1 : 0;
+  const int64_t shi = k < S - 1 ? k : S - 1;
+  float d = 0.f;
+  for (int64_t s = slo; s <= shi; ++s) d = fmaf(dM[e - s * N], g[s], d);
+  const float a = A[e];
+  const float f = a > 0.f ? d / a : 0.f;
+  re[e] *= f;
+  im[e] *= f;
+}
+
+// k_update_conv_phase restated for the Fourier model (see the header comment); the reference's sum is
+//   loss_rec + L2(Bcp_w) + L2(Bcp_n) + loss_spectral + loss_smoothness          (…py:1281)
+struct FourierLam {
+  float v[4];  // by arena factor: Bd, Bo, Kn, Ks
+};
+
+__global__ __launch_bounds__(1024) void k_update_conv_fourier(FactorSet fs, int n_bias, FourierLam lam, PhaseSmooth sm,
+                                                              int W, int Rn, int RsC,
+                                                              const float* __restrict__ spec_val,
+                                                              float* __restrict__ params,
+                                                              const float* __restrict__ grad, UpdateArgs ua,
+                                                              float* __restrict__ m, float* __restrict__ v,
+                                                              float* __restrict__ vmax,
+                                                              float* __restrict__ grad_total_out,
+                                                              float* __restrict__ loss_out,
+                                                              double* __restrict__ loss_hist,
+                                                              int32_t* __restrict__ stop) {
+#pragma clang fp contract(off)
+  __shared__ float wsum[4 * 16];
+  __shared__ float norms[4];
+  __shared__ float coef[4];
+  __shared__ float ssum[2 * 16];
+  __shared__ float sval[2];
+  extern __shared__ float sd[];  // Delta^q of [Kn | Ks], (W + q) x (Rn + Rs C)
+  const int t = threadIdx.x, lane = t & 63, q = t >> 6;
+  const int64_t nfe = fs.nfelem, np = nfe + n_bias;
+  const bool checked = ua.mode == 0 && stop != nullptr;
+  const int32_t stop0 = stop != nullptr ? *stop : 0;
+  const float status = checked ? grad[np + 1] : 0.f;
+  auto factor_of = [&](int64_t e) {
+    int f = 0;
+#pragma unroll
+    for (int g = 1; g < 4; ++g)
+      if (e >= fs.off[g]) f = g;
+    return f;
+  };
+  float accn[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t k = t; k < nfe; k += 1024) {
+    const float a = params[k];
+    const int f = factor_of(k);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
+  }
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const float r = tr_wave_allreduce(accn[f]);
+    if (lane == 0) wsum[f * 16 + q] = r;
+  }
+  // Delta^q of the raw kernels and the two sums of its squares
+  const int ord = sm.order, Wq = W + ord, Rk = Rn + RsC;
+  float accs[2] = {0.f, 0.f};
+  for (int idx = t; idx < Wq * Rk; idx += 1024) {
+    const int i = idx / Rk, c = idx - i * Rk;
+    const float* col = c < Rn ? params + fs.off[2] + c : params + fs.off[3] + (c - Rn);
+    const int ld = c < Rn ? Rn : RsC;
+    float d = 0.f;
+    for (int j = 0; j <= ord; ++j) {
+      const int w = i - j;
+      if (w >= 0 && w < W) d = d + sm.c[j] * col[(int64_t)w * ld];
+    }
+    sd[idx] = d;
+    if (c < Rn)
+      accs[0] = fmaf(d, d, accs[0]);
+    else
+      accs[1] = fmaf(d, d, accs[1]);
+  }
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const float r = tr_wave_allreduce(accs[f]);
+    if (lane == 0) ssum[f * 16 + q] = r;
+  }
+  __syncthreads();
+  if (t < 4) {
+    float tot = 0.f;
+    for (int w = 0; w < 16; ++w) tot += wsum[t * 16 + w];
+    norms[t] = sqrtf(tot);
+    coef[t] = lam.v[t] / (2.0f * norms[t]);
+  } else if (t >= 64 && t < 66) {
+    const int f = t - 64;
+    float tot = 0.f;
+    for (int w = 0; w < 16; ++w) tot += ssum[f * 16 + w];
+    const int rf = f == 0 ? Rn : RsC;
+    sval[f] = rf > 0 ? (tot / (float)(Wq * rf)) * sm.lam : 0.f;  // torch.mean(...) * lambda_smooth
+  }
+  __syncthreads();
+  if (stop0 != 0) return;
+  if (checked && status != 0.0f) {
+    if (t == 0) *stop = TR_STOP_DEVICE_ERROR - (int32_t)ua.iter;
+    return;
+  }
+  const bool adam = ua.mode != 1;
+  const bool ams = adam && ua.amsgrad;
+  for (int64_t e = t; e < np; e += 1024) {
+    float g = grad[e], p = params[e];
+    if (e < nfe) {
+      const int f = factor_of(e);
+      g = g + coef[f] * (2.0f * p);
+      if (f >= 2) {
+        const int rf = f == 2 ? Rn : RsC;
+        const int le = (int)(e - fs.off[f]);
+        const int w = le / rf, c = (f == 2 ? 0 : Rn) + (le - w * rf);
+        float gs = 0.f;
+        for (int j = 0; j <= ord; ++j) gs = gs + sm.c[j] * sd[(w + j) * Rk + c];
+        g = g + (2.0f * sm.lam / (float)(Wq * rf)) * gs;
+      }
+    }
+    if (!adam) {
+      grad_total_out[e] = g;
+      continue;
+    }
+    float mm = m[e], vv = v[e], vm = ams ? vmax[e] : 0.f;
+    g = ua.weight_decay != 0.0f ? fmaf(p, ua.weight_decay, g) : g;
+    mm = fmaf(ua.one_minus_b1, g - mm, mm);
+    vv = vv * ua.beta2;
+    vv = vv + ua.one_minus_b2 * g * g;
+    vm = fmaxf(vm, vv);
+    if (ams) vmax[e] = vm;
+    const float denom = sqrtf(ams ? vm : vv) / ua.bc2_sqrt + ua.eps;
+    p = p + (-ua.step_size) * (mm / denom);
+    m[e] = mm;
+    v[e] = vv;
+    params[e] = p;
+  }
+  if (t == 0) {
+    const float pw = (0.f + norms[2] * lam.v[2]) + norms[3] * lam.v[3];
+    const float pn = (0.f + norms[0] * lam.v[0]) + norms[1] * lam.v[1];
+    const float spec = spec_val != nullptr ? *spec_val : 0.f;
+    float ps = 0.f;  // an empty factor is skipped (comp.numel() > 0, …py:875)
+    if (Rn > 0) ps = ps + sval[0];
+    if (RsC > 0) ps = ps + sval[1];
+    const float total = (((grad[np] + pw) + pn) + spec) + ps;
+    if (loss_out != nullptr) *loss_out = total;
+    if (ua.mode == 0 && loss_hist != nullptr) loss_hist[ua.hist_base + ua.iter] = (double)total;
+    // the reference tests the plateau once len(loss_running) > patience, else the NaN stop (…py:1313-1320)
+    if (ua.mode == 0 && ua.nan_stop && stop != nullptr && ua.hist_base + ua.iter + 1 <= ua.patience &&
+        __builtin_isnan(total))
+      *stop = -(int32_t)(ua.iter + 1);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t UPD_LDS_MAX = (size_t)(CONV_MAXW + PHASE_MAXQ) * CONV_MAXK * 4;
+
+// splits of the summation range and rows per split (a multiple of the tile)
+void dft_split(int64_t A, int64_t B, int N, int* nsplit, int64_t* bper) {
+  const int64_t wg = ((A + DFT_T - 1) / DFT_T) * ((N + DFT_NC - 1) / DFT_NC);
+  const int64_t tiles = (B + DFT_BT - 1) / DFT_BT;
+  int64_t s = (1024 + wg - 1) / wg;
+  if (s > SPEC_MAXSPLIT) s = SPEC_MAXSPLIT;
+  if (s > tiles) s = tiles;
+  if (s < 1) s = 1;
+  const int64_t tper = (tiles + s - 1) / s;
+  *bper = tper * DFT_BT;
+  *nsplit = (int)((tiles + tper - 1) / tper);
+}
+
+size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+template <int ADJ>
+hipError_t launch_dft(const SpecPen& sp, const SpecBufs& b, int64_t A, int64_t B, const float* in0, const float* in1,
+                      float* out0, float* out1, float* mag, const int32_t* stop, hipStream_t st) {
+  int nsplit;
+  int64_t bper;
+  dft_split(A, B, sp.N, &nsplit, &bper);
+  const dim3 grid((unsigned)((A + DFT_T - 1) / DFT_T), (unsigned)((sp.N + DFT_NC - 1) / DFT_NC), (unsigned)nsplit);
+  hipLaunchKernelGGL(k_dft<ADJ>, grid, dim3(DFT_T), 0, st, A, B, sp.N, (uint32_t)sp.nfft, bper, b.tw, in0, in1, b.part,
+                     stop);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int64_t AN = A * sp.N;
+  hipLaunchKernelGGL(k_dft_combine<ADJ ? 0 : 1>, dim3((unsigned)((AN + 255) / 256)), dim3(256), 0, st, nsplit, AN,
+                     b.part, out0, out1, mag, stop);
+  return hipGetLastError();
+}
+}  // namespace
+
+size_t spec_carve(const SpecPen& sp, int64_t max_rows, char* base, SpecBufs* b) {
+  const size_t FN = (size_t)sp.F * sp.N, FsN = (size_t)sp.Fs * sp.N, RN = (size_t)max_rows * sp.N;
+  const size_t amax = FN > RN ? FN : RN;
+  // splits * outputs <= 2^20 + A N (dft_split: splits <= 1024 / workgroups + 1, workgroups >= A N / 1024)
+  const size_t b_part = al256(2 * (((size_t)1 << 20) + amax) * 8);
+  const size_t b_pp = al256(((FsN + PEN_EPB - 1) / PEN_EPB) * 8);
+  const size_t sz[] = {al256((size_t)sp.nfft * 8), al256((size_t)sp.S * 4), al256(FN * 4), al256(FN * 4),
+                       al256(FN * 4), al256(FsN * 4), al256(FsN * 4), al256(FsN * 4), b_part, b_pp, 256,
+                       al256(RN * 4), al256(RN * 4)};
+  size_t off[14];
+  off[0] = 0;
+  for (int i = 0; i < 13; ++i) off[i + 1] = off[i] + sz[i];
+  if (base != nullptr && b != nullptr) {
+    b->tw = (float2*)(base + off[0]);
+    b->g = (float*)(base + off[1]);
+    b->re = (float*)(base + off[2]);
+    b->im = (float*)(base + off[3]);
+    b->A = (float*)(base + off[4]);
+    b->M = (float*)(base + off[5]);
+    b->My = (float*)(base + off[6]);
+    b->dM = (float*)(base + off[7]);
+    b->part = (double*)(base + off[8]);
+    b->ppart = (double*)(base + off[9]);
+    b->val = (float*)(base + off[10]);
+    b->yhat = (float*)(base + off[11]);
+    b->eadd = (float*)(base + off[12]);
+  }
+  return off[13];
+}
+
+void spec_build_twiddles(int64_t nfft, float2* tw) {
+  const double pi = 3.14159265358979323846;
+  for (int64_t i = 0; i < nfft; ++i) {
+    const double th = 2.0 * pi * (double)i / (double)nfft;
+    tw[i] = make_float2((float)std::cos(th), (float)std::sin(th));
+  }
+}
+
+hipError_t launch_spectrum(const SpecPen& sp, const SpecBufs& b, const float* series, int64_t rows, float* M_out,
+                           const int32_t* stop, hipStream_t st) {
+  if (rows < 1 || rows > sp.nfft || sp.Fs < 1) return hipErrorInvalidValue;
+  hipError_t e = launch_dft<0>(sp, b, sp.F, rows, series, nullptr, b.re, b.im, b.A, stop, st);
+  if (e != hipSuccess) return e;
+  const int64_t FsN = sp.Fs * sp.N;
+  hipLaunchKernelGGL(k_spec_smooth, dim3((unsigned)((FsN + 255) / 256)), dim3(256), 0, st, FsN, sp.N, sp.S, b.A, b.g,
+                     M_out, stop);
+  return hipGetLastError();
+}
+
+hipError_t launch_spectrum_penalty(const SpecPen& sp, const SpecBufs& b, const float* series, int64_t rows,
+                                   float* grad_out, const int32_t* stop, hipStream_t st) {
+  hipError_t e = launch_spectrum(sp, b, series, rows, b.M, stop, st);
+  if (e != hipSuccess) return e;
+  const int64_t FsN = sp.Fs * sp.N, FN = sp.F * sp.N;
+  const int nb = (int)((FsN + PEN_EPB - 1) / PEN_EPB);
+  const float coef = (float)(2.0 * (double)sp.lam / (double)FsN);
+  hipLaunchKernelGGL(k_spec_pen, dim3(nb), dim3(256), 0, st, FsN, coef, b.M, b.My, b.dM, b.ppart, stop);
+  hipLaunchKernelGGL(k_spec_val, dim3(1), dim3(64), 0, st, nb, (double)FsN, sp.lam, b.ppart, b.val, stop);
+  hipLaunchKernelGGL(k_spec_back, dim3((unsigned)((FN + 255) / 256)), dim3(256), 0, st, sp.F, sp.Fs, sp.N, sp.S, b.dM,
+                     b.g, b.A, b.re, b.im, stop);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_dft<1>(sp, b, rows, sp.F, b.re, b.im, grad_out, nullptr, nullptr, stop, st);
+}
+
+hipError_t spectrum_prepare() {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_conv_fourier),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)UPD_LDS_MAX);
+}
+
+hipError_t launch_update_conv_fourier(const FactorSet& fs, int n_bias, const float lam[4], const PhaseSmooth& sm, int W,
+                                      int Rn, int RsC, const float* spec_val, float* params, const float* grad,
+                                      const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
+                                      float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st) {
+  if (fs.nf != 4 || sm.order < 0 || sm.order > PHASE_MAXQ || W > CONV_MAXW || Rn + RsC > CONV_MAXK)
+    return hipErrorInvalidValue;
+  FourierLam l;
+  for (int i = 0; i < 4; ++i) l.v[i] = lam[i];
+  const size_t lds = (size_t)(W + sm.order) * (Rn + RsC) * 4;
+  hipLaunchKernelGGL(k_update_conv_fourier, dim3(1), dim3(1024), lds, st, fs, n_bias, l, sm, W, Rn, RsC, spec_val,
+                     params, grad, ua, m, v, vmax, grad_total_out, loss_out, loss_hist, stop);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int64_t n_losses = ua.hist_base + ua.iter + 1;
+  if (ua.mode == 0 && loss_hist != nullptr && stop != nullptr && ua.patience >= 0 && n_losses > ua.patience &&
+      ua.tol > 0.0)
+    e = launch_converge_tail(loss_hist, n_losses, ua.iter, ua.patience, ua.tol, stop, st);
+  return e;
+}
+
+}  // namespace tr
