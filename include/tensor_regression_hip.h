@@ -234,6 +234,63 @@ int tr_adam_step(tr_plan* plan, float* params, const float* grad, float* exp_avg
                  int64_t patience, double tol, int32_t* stop_flag, void* stream);
 
 /*
+ * tr_adam_step for torch.optim.Adam with one param group per factor (the hierarchical
+ * multinomial module, multinomial_tensor_regression_hierarchical.py:436-440); float32
+ * multinomial plans only.  Same arguments and bookkeeping as tr_adam_step, except
+ *   lr            n_factors doubles (>= 0), the learning rate of each factor's group; lr 0 keeps
+ *                 torch's meaning (the moments advance, the parameters do not move)
+ *   n_factors     must equal the plan's number of factors
+ *   stepped_mask  bit f set: factor f is in a param group.  A factor outside the mask is a tensor
+ *                 the optimizer was never given: its parameters and exp_avg / exp_avg_sq /
+ *                 max_exp_avg_sq entries stay bitwise untouched, while its norm still enters the
+ *                 recorded loss (and tr_finalize_grad's total gradient is unaffected).
+ * All groups share the step count `step`.  With every factor stepped at one lr the result is
+ * bitwise tr_adam_step's.  The next-iteration preparation of tr_plan_set_prepare_next is not
+ * folded into this step (the following tr_loss_grad prepares its own factors).
+ */
+int tr_adam_step_groups(tr_plan* plan, float* params, const float* grad, float* exp_avg,
+                        float* exp_avg_sq, float* max_exp_avg_sq, float lambda_l2, const double* lr,
+                        int n_factors, uint32_t stepped_mask, double beta1, double beta2, double eps,
+                        double weight_decay, int amsgrad, int64_t step, double* loss_hist,
+                        int64_t hist_base, int64_t iter, int64_t patience, double tol,
+                        int32_t* stop_flag, void* stream);
+
+/*
+ * Resident fit of the hierarchical multinomial module: ONE workgroup on one CU holds X, the dense
+ * coefficient tensor, Z / dZ, the factors and the Adam state in LDS and runs up to 64 complete
+ * fit_Adam iterations per launch (forward, double softmax + unweighted CE, X^T dZ, factor gradients,
+ * L2 term, the grouped Adam step, loss record, plateau test); parameters and state go back to
+ * global memory at the end of the launch.  fp32 fmaf sums in one fixed order, the loss in fp64, no
+ * atomics: bitwise reproducible, and independent of how a fit is cut into launches.
+ *
+ * The envelope: a float32 multinomial plan with exactly two feature modes, n_classes <= 16,
+ * rank <= 16, and the LDS image of the plan's max_rows samples within 160 KiB.
+ *   tr_mnl_resident_max_rows  the largest n_rows inside the envelope for (I0, I1) features,
+ *                             n_classes and rank; 0 when no n_rows fits
+ *   tr_plan_set_resident      enable = 1: take the route if the plan is inside the envelope and the
+ *                             environment does not say TR_MNL_RESIDENT=0 (a test-facing switch);
+ *                             tr_plan_describe then carries "fit=resident".  Outside the envelope
+ *                             the call succeeds and the plan stays on the streamed route
+ *                             (tr_loss_grad + tr_adam_step_groups).  enable = 0: streamed route.
+ *   tr_fit_adam_resident      n_iters (1..64) iterations from loop index `iter`, whose Adam step
+ *                             count is `step`, `step + 1`, ...; lr[3] are the learning rates of the
+ *                             three factors' param groups, constant over the launch (the caller
+ *                             cuts a chunk at a schedule breakpoint).  target: int64 labels.  X is
+ *                             read at the plan's row stride.  loss_hist / hist_base / patience / tol /
+ *                             stop_flag as tr_adam_step: on a plateau the launch stops after that
+ *                             iteration's step and writes *stop_flag = iterations completed.  A
+ *                             launch that finds *stop_flag != 0 does nothing.
+ */
+int64_t tr_mnl_resident_max_rows(int64_t I0, int64_t I1, int n_classes, int rank);
+int tr_plan_set_resident(tr_plan* plan, int enable);
+int tr_fit_adam_resident(tr_plan* plan, const float* X, int64_t n_rows, const void* target, float* params,
+                         const float* weights, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                         float lambda_l2, const double* lr, double beta1, double beta2, double eps,
+                         double weight_decay, int amsgrad, int64_t step, int n_iters, double* loss_hist,
+                         int64_t hist_base, int64_t iter, int64_t patience, double tol, int32_t* stop_flag,
+                         void* stream);
+
+/*
  * Fold the NEXT iteration's factor preparation into tr_adam_step: with enable = 1, on a plan
  * that takes the factored multinomial single pass, every tr_adam_step also computes
  * softplus(A_k) and its derivative from the parameters it has just written, and the following

@@ -9,6 +9,7 @@ loop runs as hand-written HIP kernels behind the C ABI in include/tensor_regress
 from . import _lib  # noqa: F401
 from . import standard_tensor_regression  # noqa: F401
 from . import multinomial_tensor_regression  # noqa: F401
+from . import multinomial_tensor_regression_hierarchical  # noqa: F401
 from . import spectral_tensor_regression  # noqa: F401
 from . import convolutional_fourier_tensor_regression  # noqa: F401
 from .standard_tensor_regression import CP_linear_regression  # noqa: F401

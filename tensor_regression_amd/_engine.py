@@ -413,6 +413,38 @@ class Plan:
                      int(patience), float(tol), ptr(stop), stream_handle(self.dev))
         check(rc, "tr_adam_step" + self._sfx)
 
+    def adam_step_groups(self, arena, grad, m, v, vmax, lambda_l2, hp, group_lr, stepped, step, hist, hist_base,
+                         it, patience, tol, stop):
+        """tr_adam_step_groups: adam_step with one learning rate per factor (`group_lr`, n_factors
+        floats; hp["lr"] is not read) and only the factors listed in `stepped` in a param group."""
+        lrs = (ctypes.c_double * self.n_factors)(*[float(x) for x in group_lr])
+        mask = sum(1 << int(f) for f in stepped)
+        rc = self.lib.tr_adam_step_groups(self.h, ptr(arena), ptr(grad), ptr(m), ptr(v), ptr(vmax),
+                                          float(lambda_l2), lrs, self.n_factors, mask, hp["beta1"], hp["beta2"],
+                                          hp["eps"], hp["weight_decay"], 1 if hp["amsgrad"] else 0, int(step),
+                                          ptr(hist), int(hist_base), int(it), int(patience), float(tol), ptr(stop),
+                                          stream_handle(self.dev))
+        check(rc, "tr_adam_step_groups")
+
+    def set_resident(self, enable):
+        """tr_plan_set_resident: take the resident fit where the plan is inside its envelope (and
+        TR_MNL_RESIDENT is not 0).  Returns whether the plan is on the resident route now."""
+        check(self.lib.tr_plan_set_resident(self.h, 1 if enable else 0), "tr_plan_set_resident")
+        self.describe = self.lib.tr_plan_describe(self.h).decode()
+        return "fit=resident" in self.describe
+
+    def fit_resident(self, X, target, arena, weights, m, v, vmax, lambda_l2, hp, group_lr, step, n_iters, hist,
+                     hist_base, it, patience, tol, stop):
+        """tr_fit_adam_resident: n_iters (<= 64) whole iterations from loop index `it` in one launch."""
+        self._set_stride(X)
+        lrs = (ctypes.c_double * 3)(*[float(x) for x in group_lr[:3]])
+        rc = self.lib.tr_fit_adam_resident(self.h, ptr(X), X.shape[0], ptr(target), ptr(arena), ptr(weights), ptr(m),
+                                           ptr(v), ptr(vmax), float(lambda_l2), lrs, hp["beta1"], hp["beta2"],
+                                           hp["eps"], hp["weight_decay"], 1 if hp["amsgrad"] else 0, int(step),
+                                           int(n_iters), ptr(hist), int(hist_base), int(it), int(patience),
+                                           float(tol), ptr(stop), stream_handle(self.dev))
+        check(rc, "tr_fit_adam_resident")
+
 
 class SpectralPlan(Plan):
     """`tr_plan` of the spectral model (spectral_tensor_regression.CP_linear_regression):
@@ -1197,6 +1229,59 @@ def run_adam_fit(plan, X, target, class_weight, norm, arena, weights, lambda_L2,
         if prep_next:
             plan.set_prepare_next(False)
     # stop flag: > 0 plateau convergence after that many iterations; < 0 NaN stop (spectral)
+    n_run = abs(stopped_at) if stopped_at else ii
+    loss_running.extend(hist[base:base + n_run].tolist())
+    plan.last_stop = stopped_at
+    return stopped_at > 0, n_run
+
+
+def run_adam_fit_groups(plan, X, target, class_weight, norm, arena, weights, lambda_L2, max_iter, tol, patience,
+                        hp, loss_running, lr_at, stepped, verbose_cb=None, sync_every=64, resident=False,
+                        breaks=()):
+    """run_adam_fit for an optimizer with one param group per factor (the hierarchical multinomial
+    module): `lr_at(ii)` gives the n_factors learning rates in force at loop index ii, `stepped` the
+    factors that are in a param group (the others get no step and no Adam state, but stay in the
+    gradient and in the L2 term of the recorded loss).  Single device.  Streamed route: the plan's
+    loss_grad, then tr_adam_step_groups, per iteration.  resident: the plan is on the resident route
+    (Plan.set_resident) and each chunk of up to `sync_every` (<= 64) iterations is ONE launch, cut
+    at the loop indices in `breaks` (where a learning rate changes: lr is constant per launch).
+    Returns (convergence_reached, number_of_iterations_run)."""
+    dev = plan.device_str
+    grad, m, v, vmax, stop, tmp = fit_state(plan, torch.float32, hp["amsgrad"])
+    base = len(loss_running)
+    hist = torch.empty(base + max(int(max_iter), 0) + 1, dtype=torch.float64, device=dev)
+    if base and tol > 0:
+        hist[:base] = torch.tensor(loss_running, dtype=torch.float64)
+    if verbose_cb is not None:
+        sync_every = 1
+    ii = 0
+    stopped_at = 0
+    while ii < max_iter:
+        n = min(sync_every, max_iter - ii)
+        if resident:
+            nxt = [b for b in breaks if ii < b < ii + n]
+            if nxt:
+                n = min(nxt) - ii
+            plan.fit_resident(X, target, arena, weights, m, v, vmax, lambda_L2, hp, lr_at(ii), ii + 1, n, hist, base,
+                              ii, patience, tol, stop)
+        else:
+            for it in range(ii, ii + n):
+                loss_grad_any(plan, X, target, class_weight, norm, arena, weights, grad, stop=stop, tmp=tmp)
+                plan.adam_step_groups(arena, grad, m, v, vmax, lambda_L2, hp, lr_at(it), stepped, it + 1, hist, base,
+                                      it, patience, tol, stop)
+        ii += n
+        stopped_at = int(stop.item())  # one host sync per chunk
+        if stopped_at <= _lib.TR_STOP_DEVICE_ERROR:  # as in _adam_loop: resume that iteration on two passes
+            failed = _lib.TR_STOP_DEVICE_ERROR - stopped_at
+            plan.recover(f"iteration {failed}")
+            stop.zero_()
+            ii, stopped_at = failed, 0
+            continue
+        plan.check_status()
+        if verbose_cb is not None:
+            verbose_cb.after_step(ii - 1, float(hist[base + ii - 1].item()))
+        if stopped_at:
+            break
     n_run = abs(stopped_at) if stopped_at else ii
     loss_running.extend(hist[base:base + n_run].tolist())
     plan.last_stop = stopped_at

@@ -73,6 +73,15 @@ SIGNATURES = {
     "tr_adam_step": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_float, _c.c_double, _c.c_double,
                                 _c.c_double, _c.c_double, _c.c_double, _c.c_int, _c.c_int64, _vp,
                                 _c.c_int64, _c.c_int64, _c.c_int64, _c.c_double, _vp, _vp]),
+    "tr_adam_step_groups": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_float, _c.POINTER(_c.c_double), _c.c_int,
+                                       _c.c_uint32, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_int,
+                                       _c.c_int64, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_double, _vp, _vp]),
+    "tr_mnl_resident_max_rows": (_c.c_int64, [_c.c_int64, _c.c_int64, _c.c_int, _c.c_int]),
+    "tr_plan_set_resident": (_c.c_int, [_vp, _c.c_int]),
+    "tr_fit_adam_resident": (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_float,
+                                        _c.POINTER(_c.c_double), _c.c_double, _c.c_double, _c.c_double, _c.c_double,
+                                        _c.c_int, _c.c_int64, _c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int64,
+                                        _c.c_double, _vp, _vp]),
     "tr_plan_set_prepare_next": (_c.c_int, [_vp, _c.c_int]),
     "tr_plan_create_f64": (_c.c_int, [_c.POINTER(_vp), _c.c_int, _c.c_int, _c.POINTER(_c.c_int64), _c.c_int,
                                       _c.c_int64, _c.POINTER(_c.c_int32), _c.c_double, _c.c_double]),

@@ -115,6 +115,17 @@ hipError_t launch_update(const FactorSet& fs, int n_bias, float* params, const f
                          const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
                          float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st,
                          const PrepArgs* prep = nullptr);
+// Per-factor scalars of one k_update_groups launch (torch.optim.Adam with one param group per
+// factor): step_size[f] = lr_f / (1 - b1^t) rounded to fp32 like UpdateArgs::step_size; bit f of
+// mask set = factor f is in a param group (stepped), clear = left bitwise untouched.
+struct GroupArgs {
+  float step_size[TR_MAXF];
+  unsigned mask;
+};
+// k_update's Adam step with per-factor learning rates and a stepped-factor mask (no bias entries)
+hipError_t launch_update_groups(const FactorSet& fs, float* params, const float* grad, const UpdateArgs& ua,
+                                const GroupArgs& ga, float* m, float* v, float* vmax, double* loss_hist,
+                                int32_t* stop, hipStream_t st);
 // the plateau test alone (fit_Adam's stop rule, standard…py:467-470) on the fp64 loss history
 hipError_t launch_converge(const double* loss_hist, int64_t hist_base, int64_t iter, int64_t patience, double tol,
                            int32_t* stop, hipStream_t st);

@@ -24,6 +24,7 @@
 
 #include "tr_common.h"
 #include "tr_kernels.h"
+#include "tr_np_sum.h"  // np_pairwise_sum_absdiff (k_converge, k_converge_tail)
 
 namespace tr {
 
@@ -51,70 +52,6 @@ __device__ __forceinline__ int factor_of(const FactorSet& fs, int64_t e) {
   return f;
 }
 }
-
-namespace {
-// sum_{j<n} |h[j+1] - h[j]| in the order of numpy's DOUBLE_pairwise_sum (PW_BLOCKSIZE 128, 8
-// accumulators), iterative over the recursion tree (left-first), n <= NP_BUFSIZE.
-__device__ double np_pairwise_block_absdiff(const double* h, int64_t n) {
-  double total = 0.0;
-  // explicit stack of (start, len, depth-combine) — emulate recursion with partial sums
-  struct Frame { int64_t s, n; int state; double left; };
-  Frame st[48];
-  int sp = 0;
-  st[sp++] = {0, n, 0, 0.0};
-  double ret = 0.0;
-  while (sp > 0) {
-    Frame& fr = st[sp - 1];
-    if (fr.n <= 128 && fr.state == 0) {
-      const int64_t s = fr.s, m = fr.n;
-      double res;
-      if (m < 8) {
-        res = -0.0;
-        for (int64_t i = 0; i < m; ++i) res += fabs(h[s + i + 1] - h[s + i]);
-      } else {
-        double r[8];
-        for (int j = 0; j < 8; ++j) r[j] = fabs(h[s + j + 1] - h[s + j]);
-        int64_t i = 8;
-        for (; i < m - (m % 8); i += 8)
-          for (int j = 0; j < 8; ++j) r[j] += fabs(h[s + i + j + 1] - h[s + i + j]);
-        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < m; ++i) res += fabs(h[s + i + 1] - h[s + i]);
-      }
-      ret = res;
-      --sp;
-      continue;
-    }
-    int64_t n2 = fr.n / 2;
-    n2 -= n2 % 8;
-    if (fr.state == 0) {
-      fr.state = 1;
-      st[sp++] = {fr.s, n2, 0, 0.0};
-    } else if (fr.state == 1) {
-      fr.left = ret;
-      fr.state = 2;
-      const int64_t s = fr.s + n2, m = fr.n - n2;
-      st[sp++] = {s, m, 0, 0.0};
-    } else {
-      ret = fr.left + ret;
-      --sp;
-    }
-  }
-  total = ret;
-  return total;
-}
-constexpr int64_t NP_BUFSIZE = 8192;  // numpy's ufunc buffer, in elements (np.getbufsize() default)
-}  // namespace
-
-// np.sum(np.abs(np.diff(h[0 : n + 1]))) as numpy adds it up: the reduction takes its operand in
-// chunks of NP_BUFSIZE elements, sums each chunk pairwise and adds the chunk sums to the running
-// result one after another (up to 8192 terms: one pairwise sum).
-__device__ double np_pairwise_sum_absdiff(const double* h, int64_t n) {
-  double total = -0.0;  // the identity numpy's add reduction starts from
-  for (int64_t c = 0; c < n; c += NP_BUFSIZE)
-    total += np_pairwise_block_absdiff(h + c, n - c < NP_BUFSIZE ? n - c : NP_BUFSIZE);
-  return total;
-}
-
 
 __global__ __launch_bounds__(UPD_T) void k_update(FactorSet fs, int n_bias,
                                                   float* __restrict__ params, const float* __restrict__ grad,
@@ -571,6 +508,120 @@ hipError_t launch_update(const FactorSet& fs, int n_bias, float* params, const f
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (ua.mode == 0 && loss_hist != nullptr && stop != nullptr && ua.iter > ua.patience && ua.tol > 0.0) {
+    hipLaunchKernelGGL(k_converge, dim3(1), dim3(64), 0, st, loss_hist, ua.hist_base, ua.iter, ua.patience,
+                       ua.tol, stop);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
+// ==========================================================================================
+// k_update restated for torch.optim.Adam with one param group per factor
+// (multinomial_tensor_regression_hierarchical.py:436-440): every factor f has its own step size
+// lr_f / (1 - b1^t) and a stepped flag.  A factor outside the mask is a tensor the optimizer was
+// never given: its gradient (data + L2) exists and its norm enters the recorded loss, but its
+// parameters and m / v / vmax are neither read for the step nor written.  Same norm order (thread
+// t sums the elements k = t (mod 1024) in increasing k, wave butterfly, wave-order LDS sum), same
+// _single_tensor_adam sequence and one shared step count t as k_update; with every factor in the
+// mask at one lr the results are bitwise k_update's.  Adam only (mode 0), no bias entries, no
+// next-iteration preparation.
+// ==========================================================================================
+__global__ __launch_bounds__(UPD_T) void k_update_groups(FactorSet fs, float* __restrict__ params,
+                                                         const float* __restrict__ grad, UpdateArgs ua,
+                                                         GroupArgs ga, float* __restrict__ m, float* __restrict__ v,
+                                                         float* __restrict__ vmax, double* __restrict__ loss_hist,
+                                                         int32_t* __restrict__ stop) {
+#pragma clang fp contract(off)
+  __shared__ float wsum[TR_MAXF * 16];
+  __shared__ float norms[TR_MAXF];
+  __shared__ float coef[TR_MAXF];
+  __shared__ float ssize[TR_MAXF];
+  const int t = threadIdx.x;
+  const int lane = t & (TR_WAVE - 1);
+  const int q = t / TR_WAVE;
+  constexpr int NWV = UPD_T / TR_WAVE;
+  constexpr int64_t B = UPD_T;
+  const int64_t np = fs.nfelem;
+  const bool checked = stop != nullptr;
+  const int32_t stop0 = stop != nullptr ? *stop : 0;
+  const float status = checked ? grad[np + 1] : 0.f;
+  float accn[TR_MAXF];
+#pragma unroll
+  for (int f = 0; f < TR_MAXF; ++f) accn[f] = 0.f;
+  auto acc = [&](int64_t k, float a) {
+    const int f = factor_of(fs, k);
+#pragma unroll
+    for (int g = 0; g < TR_MAXF; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
+  };
+  int64_t k = t;
+  for (; k + (UPD_TRIP - 1) * B < np; k += UPD_TRIP * B) {
+    float a[UPD_TRIP];
+#pragma unroll
+    for (int u = 0; u < UPD_TRIP; ++u) a[u] = params[k + u * B];
+#pragma unroll
+    for (int u = 0; u < UPD_TRIP; ++u) acc(k + u * B, a[u]);
+  }
+  for (; k < np; k += B) acc(k, params[k]);
+#pragma unroll
+  for (int f = 0; f < TR_MAXF; ++f) {
+    if (f < fs.nf) {
+      const float r = tr_wave_allreduce(accn[f]);
+      if (lane == 0) wsum[f * 16 + q] = r;
+    }
+  }
+  __syncthreads();
+  if (t < fs.nf) {
+    float tot = 0.f;
+    for (int w = 0; w < NWV; ++w) tot += wsum[t * 16 + w];
+    norms[t] = sqrtf(tot);
+    coef[t] = ua.lambda_l2 / (2.0f * norms[t]);
+    ssize[t] = ga.step_size[t];
+  }
+  __syncthreads();
+  if (stop0 != 0) return;
+  if (checked && status != 0.0f) {
+    if (t == 0) *stop = TR_STOP_DEVICE_ERROR - (int32_t)ua.iter;
+    return;
+  }
+  const bool ams = ua.amsgrad;
+  for (int64_t e = t; e < np; e += B) {
+    const int f = factor_of(fs, e);
+    if (!((ga.mask >> f) & 1u)) continue;  // not in any param group: parameters and state untouched
+    float p = params[e];
+    float g = grad[e] + coef[f] * (2.0f * p);
+    float mm = m[e], vv = v[e];
+    g = ua.weight_decay != 0.0f ? fmaf(p, ua.weight_decay, g) : g;  // grad.add(param, alpha=wd)
+    mm = fmaf(ua.one_minus_b1, g - mm, mm);                          // exp_avg.lerp_(grad, 1 - b1)
+    vv = vv * ua.beta2;                                              // exp_avg_sq.mul_(b2)
+    vv = vv + ua.one_minus_b2 * g * g;                               //   .addcmul_(g, g, 1 - b2)
+    float vm = 0.f;
+    if (ams) {
+      vm = fmaxf(vmax[e], vv);
+      vmax[e] = vm;
+    }
+    const float denom = sqrtf(ams ? vm : vv) / ua.bc2_sqrt + ua.eps;
+    p = p + (-ssize[f]) * (mm / denom);                              // addcdiv_(m, denom, -step_size)
+    m[e] = mm;
+    v[e] = vv;
+    params[e] = p;
+  }
+  if (t == 0) {
+    float l2 = 0.f;
+    for (int f = 0; f < fs.nf; ++f) l2 = l2 + norms[f];
+    const float total = grad[np] + ua.lambda_l2 * l2;
+    if (loss_hist != nullptr) loss_hist[ua.hist_base + ua.iter] = (double)total;
+  }
+}
+
+hipError_t launch_update_groups(const FactorSet& fs, float* params, const float* grad, const UpdateArgs& ua,
+                                const GroupArgs& ga, float* m, float* v, float* vmax, double* loss_hist,
+                                int32_t* stop, hipStream_t st) {
+  if (fs.nf < 1 || fs.nf > TR_MAXF || ua.mode != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_update_groups, dim3(1), dim3(UPD_T), 0, st, fs, params, grad, ua, ga, m, v, vmax, loss_hist,
+                     stop);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (loss_hist != nullptr && stop != nullptr && ua.iter > ua.patience && ua.tol > 0.0) {
     hipLaunchKernelGGL(k_converge, dim3(1), dim3(64), 0, st, loss_hist, ua.hist_base, ua.iter, ua.patience,
                        ua.tol, stop);
     e = hipGetLastError();
