@@ -525,12 +525,15 @@ class ConvPlan(Plan):
     Ks (W, Rs, C) | bias (N).  `lambda_l2` of finalize_grad / adam_step is the length-3 sequence
     (w, d, out) of the reference's fit_Adam."""
 
+    _model = _lib.TR_MODEL_CONV_SPECTRAL
+    _create = "tr_plan_create_conv"
+
     def __init__(self, n_w, n_d, n_out, rank_normal, rank_spectral, n_complex, max_rows, non_negative,
                  softplus_kwargs, device):
         self.lib = _lib.load()
         self.dev = device_index(device)
         self.device_str = f"cuda:{self.dev}"
-        self.model = _lib.TR_MODEL_CONV_SPECTRAL
+        self.model = self._model
         self.dtype, self.f64, self._sfx = torch.float32, False, ""
         self.dims = (int(n_w), int(n_d), int(n_out))
         self.rank_normal, self.rank_spectral, self.n_complex = int(rank_normal), int(rank_spectral), int(n_complex)
@@ -541,10 +544,9 @@ class ConvPlan(Plan):
         beta, thr = self.nonlin[1:]
         h = ctypes.c_void_p()
         with torch.cuda.device(self.dev):
-            rc = self.lib.tr_plan_create_conv(ctypes.byref(h), self.dev, self.dims[0], self.dims[1], self.dims[2],
-                                              self.rank_normal, self.rank_spectral, self.n_complex,
-                                              max(1, self.max_rows), nn, beta, thr)
-        check(rc, "tr_plan_create_conv")
+            rc = getattr(self.lib, self._create)(ctypes.byref(h), self.dev, *self._create_shape(),
+                                                 max(1, self.max_rows), nn, beta, thr)
+        check(rc, self._create)
         self.h = h
         _track(self)
         self.num_params = int(self.lib.tr_plan_num_params(h))
@@ -552,6 +554,10 @@ class ConvPlan(Plan):
         self.offsets = [int(self.lib.tr_plan_factor_offset(h, f)) for f in range(5)]
         self.describe = self.lib.tr_plan_describe(h).decode()
         self._lam = None
+
+    def _create_shape(self):
+        """The shape arguments of the create call, between the device and max_series_rows."""
+        return (*self.dims, self.rank_normal, self.rank_spectral, self.n_complex)
 
     def factor_shapes(self):
         W, D, O = self.dims
@@ -618,40 +624,13 @@ class ConvPlan(Plan):
         check(rc, "tr_adam_step")
 
 
-class ConvPhasePlan(ConvPlan):
-    """`tr_plan` of the phase-constrained convolutional model (phase_constrained_spectral_convolutional_
-    tensor_regression.CP_linear_regression): the conv plan with two spectral components of which the
-    second is derived on the device, arena = Bd (D, R) | Bo (N, R) | Kn (W, Rn) | Ks (W, Rs) | bias (N).
-    `lambda_l2` of finalize_grad / adam_step is the length-3 sequence (w, d, out); the smoothness
-    term's `lambda_smooth` / `diff_order` are plan state next to it (set_smoothness)."""
+class _SmoothConvPlan(ConvPlan):
+    """A conv plan with the smoothness term lambda_smooth * mean((Delta^q F)^2) as plan state."""
 
-    def __init__(self, n_w, n_d, n_out, rank_normal, rank_spectral, max_rows, non_negative, softplus_kwargs,
-                 device, lambda_smooth=0.0, diff_order=2):
-        self.lib = _lib.load()
-        self.dev = device_index(device)
-        self.device_str = f"cuda:{self.dev}"
-        self.model = _lib.TR_MODEL_CONV_PHASE
-        self.dtype, self.f64, self._sfx = torch.float32, False, ""
-        self.dims = (int(n_w), int(n_d), int(n_out))
-        self.rank_normal, self.rank_spectral, self.n_complex = int(rank_normal), int(rank_spectral), 1
-        self.max_rows = int(max_rows)
-        self.n_factors = 4
-        self.nonlin = nonlin_key(non_negative, softplus_kwargs, 3)
-        nn = (ctypes.c_int32 * 3)(*self.nonlin[0])
-        beta, thr = self.nonlin[1:]
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.dev):
-            rc = self.lib.tr_plan_create_conv_phase(ctypes.byref(h), self.dev, self.dims[0], self.dims[1],
-                                                    self.dims[2], self.rank_normal, self.rank_spectral,
-                                                    max(1, self.max_rows), nn, beta, thr)
-        check(rc, "tr_plan_create_conv_phase")
-        self.h = h
-        _track(self)
-        self.num_params = int(self.lib.tr_plan_num_params(h))
-        self.num_grads = int(self.lib.tr_plan_num_grads(h))
-        self.offsets = [int(self.lib.tr_plan_factor_offset(h, f)) for f in range(5)]
-        self.describe = self.lib.tr_plan_describe(h).decode()
-        self._lam = None
+    def __init__(self, n_w, n_d, n_out, rank_normal, rank_spectral, n_complex, max_rows, non_negative,
+                 softplus_kwargs, device, lambda_smooth=0.0, diff_order=2):
+        super().__init__(n_w, n_d, n_out, rank_normal, rank_spectral, n_complex, max_rows, non_negative,
+                         softplus_kwargs, device)
         self._smooth = None
         self.set_smoothness(lambda_smooth, diff_order)
 
@@ -663,43 +642,31 @@ class ConvPhasePlan(ConvPlan):
         self.lambda_smooth, self.diff_order = sm
 
 
-class ConvFourierPlan(ConvPlan):
+class ConvPhasePlan(_SmoothConvPlan):
+    """`tr_plan` of the phase-constrained convolutional model (phase_constrained_spectral_convolutional_
+    tensor_regression.CP_linear_regression): the conv plan with two spectral components of which the
+    second is derived on the device, arena = Bd (D, R) | Bo (N, R) | Kn (W, Rn) | Ks (W, Rs) | bias (N).
+    `lambda_l2` of finalize_grad / adam_step is the length-3 sequence (w, d, out); the smoothness
+    term's `lambda_smooth` / `diff_order` are plan state next to it (set_smoothness)."""
+    _model = _lib.TR_MODEL_CONV_PHASE
+    _create = "tr_plan_create_conv_phase"
+
+    def __init__(self, n_w, n_d, n_out, rank_normal, rank_spectral, max_rows, non_negative, softplus_kwargs,
+                 device, lambda_smooth=0.0, diff_order=2):
+        super().__init__(n_w, n_d, n_out, rank_normal, rank_spectral, 1, max_rows, non_negative, softplus_kwargs,
+                         device, lambda_smooth, diff_order)
+
+    def _create_shape(self):
+        return (*self.dims, self.rank_normal, self.rank_spectral)  # no component count: the pair is derived
+
+
+class ConvFourierPlan(_SmoothConvPlan):
     """`tr_plan` of the convolutional Fourier model (convolutional_fourier_tensor_regression.
     CP_linear_regression): the conv plan's arena and X pass, the phase plan's smoothness term
     (set_smoothness) and the output-spectrum penalty (set_spectrum_penalty), both plan state."""
-
-    def __init__(self, n_w, n_d, n_out, rank_normal, rank_spectral, n_complex, max_rows, non_negative,
-                 softplus_kwargs, device, lambda_smooth=0.0, diff_order=2):
-        self.lib = _lib.load()
-        self.dev = device_index(device)
-        self.device_str = f"cuda:{self.dev}"
-        self.model = _lib.TR_MODEL_CONV_FOURIER
-        self.dtype, self.f64, self._sfx = torch.float32, False, ""
-        self.dims = (int(n_w), int(n_d), int(n_out))
-        self.rank_normal, self.rank_spectral, self.n_complex = int(rank_normal), int(rank_spectral), int(n_complex)
-        self.max_rows = int(max_rows)
-        self.n_factors = 4
-        self.nonlin = nonlin_key(non_negative, softplus_kwargs, 3)
-        nn = (ctypes.c_int32 * 3)(*self.nonlin[0])
-        beta, thr = self.nonlin[1:]
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.dev):
-            rc = self.lib.tr_plan_create_conv_fourier(ctypes.byref(h), self.dev, self.dims[0], self.dims[1],
-                                                      self.dims[2], self.rank_normal, self.rank_spectral,
-                                                      self.n_complex, max(1, self.max_rows), nn, beta, thr)
-        check(rc, "tr_plan_create_conv_fourier")
-        self.h = h
-        _track(self)
-        self.num_params = int(self.lib.tr_plan_num_params(h))
-        self.num_grads = int(self.lib.tr_plan_num_grads(h))
-        self.offsets = [int(self.lib.tr_plan_factor_offset(h, f)) for f in range(5)]
-        self.describe = self.lib.tr_plan_describe(h).decode()
-        self._lam = None
-        self._smooth = None
-        self.spectrum = None  # (n_fft, n_kernel) while the penalty is on
-        self.set_smoothness(lambda_smooth, diff_order)
-
-    set_smoothness = ConvPhasePlan.set_smoothness
+    _model = _lib.TR_MODEL_CONV_FOURIER
+    _create = "tr_plan_create_conv_fourier"
+    spectrum = None  # (n_fft, n_kernel) while the penalty is on
 
     def set_spectrum_penalty(self, lam, kernel, n_fft, target):
         """lam, the smoothing kernel (1-D, host), n_fft and the (rows, n_out) device series whose smoothed

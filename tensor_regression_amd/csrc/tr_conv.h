@@ -19,6 +19,7 @@ constexpr int CONV_MAXR = 32;
 constexpr int CONV_MAXN = 64;
 constexpr int CONV_MAXK = 64;
 constexpr int CONV_MAXC = 4;
+constexpr int CONV_MAXQ = 8;     // highest difference order of the smoothness term
 
 // Column group: a run of `nr` ranks starting at rank `rbase` whose temporal kernels have `cc`
 // components each (normal ranks and spectral ranks with one component: cc = 1, signed; spectral
@@ -62,8 +63,26 @@ hipError_t launch_conv(int train, const ConvGeom& g, int grid, const float* X, i
 hipError_t launch_conv_finish(const ConvGeom& g, int nslabs, const float* gpart, const double* dpart,
                               const int32_t* gmap, const float* dphi, double loss_scale, float* grad_out,
                               const int32_t* stop, hipStream_t st);
-// L2 term with one lambda per factor (lam: Bd, Bo, Kn, Ks) + Adam / AMSGrad step + loss record + stops
-hipError_t launch_update_conv(const FactorSet& fs, int n_bias, const float lam[4], float* params, const float* grad,
+// Smoothness term lambda * mean((Delta^q F)^2) of the raw temporal kernels (Kn, Ks) of the phase and
+// Fourier models.
+struct ConvSmooth {
+  float lam;
+  int order;                // q, 0..CONV_MAXQ
+  float c[CONV_MAXQ + 1];   // (-1)^j C(q, j): the stencil of Delta^q
+};
+void conv_smooth_init(ConvSmooth* s, float lambda_smooth, int order);
+// once per process before a launch_update_conv with a smoothness term: its Delta^q scratch is dynamic
+// LDS of up to (257 + 8) x 64 floats
+hipError_t conv_update_prepare();
+// The update step of the three conv models (one kernel, k_update_conv): L2 term with one lambda per
+// factor (lam: Bd, Bo, Kn, Ks) + Adam / AMSGrad step + loss record + stops.
+//   sm         nullptr: no smoothness term (conv spectral; W, Rn, RsK are not read).  Else its value and
+//              gradient over Kn (W, Rn) and Ks seen as (W, RsK) join the total and the gradient.
+//   spec_val   nullable device scalar added to the total between the L2 terms and the smoothness term
+//   tail_rule  false: conv spectral's stops (NaN while iter <= patience, then k_converge);
+//              true: phase / Fourier's (NaN while hist_base + iter + 1 <= patience, then k_converge_tail)
+hipError_t launch_update_conv(const FactorSet& fs, int n_bias, const float lam[4], const ConvSmooth* sm, int W, int Rn,
+                              int RsK, const float* spec_val, bool tail_rule, float* params, const float* grad,
                               const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
                               float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st);
 

@@ -365,15 +365,27 @@ __global__ __launch_bounds__(256) void k_conv_finish(int64_t nparams, int64_t nf
   }
 }
 
-// The update of the convolutional model: k_update's arithmetic (tr_update.hip) with one lambda per
-// factor and the reference's order of the penalty sum,
-//   loss + L2_penalty(Bcp_w, [l0, l0]) + L2_penalty(Bcp_n, l[1:])        (…py:1046)
+// The update of the three convolutional models (conv spectral, phase-constrained, Fourier): k_update's
+// arithmetic (tr_update.hip) with one lambda per factor and the reference's order of the penalty sum,
+//   loss + L2_penalty(Bcp_w, [l0, l0]) + L2_penalty(Bcp_n, l[1:])                    (conv …py:1046)
+//   ... + loss_spectral + loss_smoothness                                 (phase …py:1412, Fourier …py:1281)
 // A kernel of its own: k_update as compiled for the other models is untouched.
+//   SMOOTH = false   the conv spectral model: no smoothness term, no dynamic LDS.
+//   SMOOTH = true    plus lambda_s mean((Delta^q F)^2) over the raw Kn (W, Rn) and Ks seen as (W, RsK)
+//                    (RsK = Rs for the phase model, Rs C for the Fourier model):
+//                    Delta^q F = F convolved (full) with the stencil (-1)^j C(q, j), W + q rows, kept in
+//                    dynamic LDS ((W + q) (Rn + RsK) floats); gradient (2 lambda_s / ((W + q) R_F))
+//                    (Delta^q)^T Delta^q F.  spec_val (nullable) is the spectrum penalty's value.
+// nan_armed: the host's decision that a NaN total stops the fit at this iteration (the two stop-rule
+// families differ in it, launch_update_conv).
 struct ConvLam {
   float v[4];  // by arena factor: Bd, Bo, Kn, Ks
 };
 
-__global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, ConvLam lam, float* __restrict__ params,
+template <bool SMOOTH>
+__global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, ConvLam lam, ConvSmooth sm, int W,
+                                                      int Rn, int RsK, const float* __restrict__ spec_val,
+                                                      int nan_armed, float* __restrict__ params,
                                                       const float* __restrict__ grad, UpdateArgs ua,
                                                       float* __restrict__ m, float* __restrict__ v,
                                                       float* __restrict__ vmax, float* __restrict__ grad_total_out,
@@ -383,6 +395,9 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
   __shared__ float wsum[4 * 16];
   __shared__ float norms[4];
   __shared__ float coef[4];
+  __shared__ float ssum[2 * 16];  // SMOOTH only (as sval and sd)
+  __shared__ float sval[2];
+  extern __shared__ float sd[];  // Delta^q of [Kn | Ks], (W + q) x (Rn + RsK)
   const int t = threadIdx.x, lane = t & 63, q = t >> 6;
   const int64_t nfe = fs.nfelem, np = nfe + n_bias;
   const bool checked = ua.mode == 0 && stop != nullptr;
@@ -407,12 +422,43 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
     const float r = tr_wave_allreduce(accn[f]);
     if (lane == 0) wsum[f * 16 + q] = r;
   }
+  const int ord = sm.order, Wq = W + ord, Rk = Rn + RsK;
+  if constexpr (SMOOTH) {
+    // Delta^q of the raw kernels and the two sums of its squares
+    float accs[2] = {0.f, 0.f};
+    for (int idx = t; idx < Wq * Rk; idx += 1024) {
+      const int i = idx / Rk, c = idx - i * Rk;
+      const float* col = c < Rn ? params + fs.off[2] + c : params + fs.off[3] + (c - Rn);
+      const int ld = c < Rn ? Rn : RsK;
+      float d = 0.f;
+      for (int j = 0; j <= ord; ++j) {
+        const int w = i - j;
+        if (w >= 0 && w < W) d = d + sm.c[j] * col[(int64_t)w * ld];
+      }
+      sd[idx] = d;
+      if (c < Rn)
+        accs[0] = fmaf(d, d, accs[0]);
+      else
+        accs[1] = fmaf(d, d, accs[1]);
+    }
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      const float r = tr_wave_allreduce(accs[f]);
+      if (lane == 0) ssum[f * 16 + q] = r;
+    }
+  }
   __syncthreads();
   if (t < 4) {
     float tot = 0.f;
     for (int w = 0; w < 16; ++w) tot += wsum[t * 16 + w];
     norms[t] = sqrtf(tot);
     coef[t] = lam.v[t] / (2.0f * norms[t]);
+  } else if (SMOOTH && t >= 64 && t < 66) {
+    const int f = t - 64;
+    float tot = 0.f;
+    for (int w = 0; w < 16; ++w) tot += ssum[f * 16 + w];
+    const int rf = f == 0 ? Rn : RsK;
+    sval[f] = rf > 0 ? (tot / (float)(Wq * rf)) * sm.lam : 0.f;  // torch.mean(...) * lambda_smooth
   }
   __syncthreads();
   if (stop0 != 0) return;
@@ -424,7 +470,18 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
   const bool ams = adam && ua.amsgrad;
   for (int64_t e = t; e < np; e += 1024) {
     float g = grad[e], p = params[e];
-    if (e < nfe) g = g + coef[factor_of(e)] * (2.0f * p);
+    if (e < nfe) {
+      const int f = factor_of(e);
+      g = g + coef[f] * (2.0f * p);
+      if (SMOOTH && f >= 2) {
+        const int rf = f == 2 ? Rn : RsK;
+        const int le = (int)(e - fs.off[f]);
+        const int w = le / rf, c = (f == 2 ? 0 : Rn) + (le - w * rf);
+        float gs = 0.f;
+        for (int j = 0; j <= ord; ++j) gs = gs + sm.c[j] * sd[(w + j) * Rk + c];
+        g = g + (2.0f * sm.lam / (float)(Wq * rf)) * gs;
+      }
+    }
     if (!adam) {
       grad_total_out[e] = g;
       continue;
@@ -445,11 +502,17 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
   if (t == 0) {
     const float pw = (0.f + norms[2] * lam.v[2]) + norms[3] * lam.v[3];
     const float pn = (0.f + norms[0] * lam.v[0]) + norms[1] * lam.v[1];
-    const float total = (grad[np] + pw) + pn;
+    float total = (grad[np] + pw) + pn;
+    if (SMOOTH) {
+      if (spec_val != nullptr) total = total + *spec_val;
+      float ps = 0.f;  // an empty factor is skipped (comp.numel() > 0, phase …py:954, Fourier …py:875)
+      if (Rn > 0) ps = ps + sval[0];
+      if (RsK > 0) ps = ps + sval[1];
+      total = total + ps;
+    }
     if (loss_out != nullptr) *loss_out = total;
     if (ua.mode == 0 && loss_hist != nullptr) loss_hist[ua.hist_base + ua.iter] = (double)total;
-    if (ua.mode == 0 && ua.nan_stop && stop != nullptr && ua.iter <= ua.patience && __builtin_isnan(total))
-      *stop = -(int32_t)(ua.iter + 1);
+    if (nan_armed && __builtin_isnan(total)) *stop = -(int32_t)(ua.iter + 1);
   }
 }
 
@@ -588,18 +651,56 @@ hipError_t launch_conv_finish(const ConvGeom& g, int nslabs, const float* gpart,
   return hipGetLastError();
 }
 
-hipError_t launch_update_conv(const FactorSet& fs, int n_bias, const float lam[4], float* params, const float* grad,
+void conv_smooth_init(ConvSmooth* s, float lambda_smooth, int order) {
+  std::memset(s, 0, sizeof(*s));
+  s->lam = lambda_smooth;
+  s->order = order;
+  double c = 1.0;  // (-1)^j C(q, j)
+  for (int j = 0; j <= order; ++j) {
+    s->c[j] = (float)c;
+    c = -c * (double)(order - j) / (double)(j + 1);
+  }
+}
+
+hipError_t conv_update_prepare() {
+  // Delta^q of the widest plan, (257 + 8) x 64 floats, is past the 64 KiB a kernel gets unasked
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_conv<true>),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (CONV_MAXW + CONV_MAXQ) * CONV_MAXK * 4);
+}
+
+hipError_t launch_update_conv(const FactorSet& fs, int n_bias, const float lam[4], const ConvSmooth* sm, int W, int Rn,
+                              int RsK, const float* spec_val, bool tail_rule, float* params, const float* grad,
                               const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
                               float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st) {
   if (fs.nf != 4) return hipErrorInvalidValue;
+  if (sm != nullptr && (sm->order < 0 || sm->order > CONV_MAXQ || W > CONV_MAXW || Rn + RsK > CONV_MAXK))
+    return hipErrorInvalidValue;
   ConvLam l;
   for (int i = 0; i < 4; ++i) l.v[i] = lam[i];
-  hipLaunchKernelGGL(k_update_conv, dim3(1), dim3(1024), 0, st, fs, n_bias, l, params, grad, ua, m, v, vmax,
-                     grad_total_out, loss_out, loss_hist, stop);
+  // The two stop-rule families.  Conv spectral (…py:1057-1064) counts this fit's iterations: the NaN stop
+  // is armed while iter <= patience, then k_converge tests the plateau.  Phase and Fourier (tail_rule; phase
+  // …py:1445-1452, Fourier …py:1313-1320) count len(loss_running): the NaN stop is armed while it is
+  // <= patience, then k_converge_tail tests the slice loss_running[-patience+1:].
+  const int64_t n_losses = ua.hist_base + ua.iter + 1;
+  const bool can_stop = ua.mode == 0 && stop != nullptr;
+  const bool early = tail_rule ? n_losses <= ua.patience : ua.iter <= ua.patience;
+  const int nan_armed = can_stop && ua.nan_stop && early;
+  if (sm != nullptr) {
+    const size_t lds = (size_t)(W + sm->order) * (Rn + RsK) * 4;
+    hipLaunchKernelGGL(k_update_conv<true>, dim3(1), dim3(1024), lds, st, fs, n_bias, l, *sm, W, Rn, RsK, spec_val,
+                       nan_armed, params, grad, ua, m, v, vmax, grad_total_out, loss_out, loss_hist, stop);
+  } else {
+    hipLaunchKernelGGL(k_update_conv<false>, dim3(1), dim3(1024), 0, st, fs, n_bias, l, ConvSmooth{}, 0, 0, 0,
+                       nullptr, nan_armed, params, grad, ua, m, v, vmax, grad_total_out, loss_out, loss_hist, stop);
+  }
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (ua.mode == 0 && loss_hist != nullptr && stop != nullptr && ua.iter > ua.patience && ua.tol > 0.0)
+  if (e != hipSuccess || !can_stop || loss_hist == nullptr || !(ua.tol > 0.0)) return e;
+  if (tail_rule) {
+    if (ua.patience >= 0 && n_losses > ua.patience)
+      e = launch_converge_tail(loss_hist, n_losses, ua.iter, ua.patience, ua.tol, stop, st);
+  } else if (ua.iter > ua.patience) {
     e = launch_converge(loss_hist, ua.hist_base, ua.iter, ua.patience, ua.tol, stop, st);
+  }
   return e;
 }
 

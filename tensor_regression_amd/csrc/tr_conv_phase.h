@@ -1,6 +1,6 @@
 // tr_conv_phase.h — host-side interface of the phase-constrained convolutional kernels
 // (tr_conv_phase.hip).  The X pass is k_conv (tr_conv.h) with C = 2; these kernels build its
-// quadrature pair, fold the pair's gradient back and add the smoothness term to the update.
+// quadrature pair and fold the pair's gradient back.  The update step is tr_conv.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,15 +12,6 @@
 
 namespace tr {
 
-constexpr int PHASE_MAXQ = 8;  // highest difference order of the smoothness term
-
-// Smoothness term lambda * mean((Delta^q F)^2) of the raw temporal kernels (Kn, Ks).
-struct PhaseSmooth {
-  float lam;
-  int order;                  // q, 0..PHASE_MAXQ
-  float c[PHASE_MAXQ + 1];    // (-1)^j C(q, j): the stencil of Delta^q
-};
-
 // ConvGeom of the phase model: conv_geom_init with C = 2 (the column groups, the slab and the LDS
 // carve of k_conv), then the arena re-laid as Bd (D, R) | Bo (N, R) | Kn (W, Rn) | Ks (W, Rs) | bias (N).
 bool phase_geom_init(ConvGeom* g, int64_t n_w, int64_t n_d, int64_t n_out, int rank_normal, int rank_spectral,
@@ -31,7 +22,6 @@ void phase_build_filter(int W, float* h2);
 // gmap[e] = slab index of arena element e; for Ks[w, s] the slab index of column 2j (its pair
 // column 2j + 1 follows)
 void phase_build_gmap(const ConvGeom& g, int32_t* gmap);
-void phase_smooth_init(PhaseSmooth* s, float lambda_smooth, int order);
 // softplus'd factors -> padded kernel columns Kp (G, W, 16); a spectral rank's two columns are
 // phi(Ks)[:, s] and H phi(Ks)[:, s]
 hipError_t launch_phase_kp(const ConvGeom& g, const float* phi, const float* h2, float* Kp, const int32_t* stop,
@@ -40,10 +30,4 @@ hipError_t launch_phase_kp(const ConvGeom& g, const float* phi, const float* h2,
 hipError_t launch_phase_finish(const ConvGeom& g, int nslabs, const float* gpart, const double* dpart,
                                const int32_t* gmap, const float* dphi, const float* h2, double loss_scale,
                                float* grad_out, const int32_t* stop, hipStream_t st);
-// launch_update_conv with the smoothness term's value and gradient added
-hipError_t launch_update_conv_phase(const FactorSet& fs, int n_bias, const float lam[4], const PhaseSmooth& sm, int W,
-                                    int Rn, int Rs, float* params, const float* grad, const UpdateArgs& ua, float* m,
-                                    float* v, float* vmax, float* grad_total_out, float* loss_out, double* loss_hist,
-                                    int32_t* stop, hipStream_t st);
-
 }  // namespace tr

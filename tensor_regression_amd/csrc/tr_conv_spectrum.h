@@ -1,5 +1,5 @@
-// tr_conv_spectrum.h — host-side interface of the output-spectrum penalty and of the convolutional
-// Fourier model's update (tr_conv_spectrum.hip).  The X pass is k_conv (tr_conv.h); these kernels
+// tr_conv_spectrum.h — host-side interface of the output-spectrum penalty of the convolutional
+// Fourier model (tr_conv_spectrum.hip).  The X pass is k_conv (tr_conv.h); these kernels
 // compute |rfft(y_hat, n_fft)| of any length by a direct real DFT, smooth it, form the penalty and
 // carry its gradient back into y_hat (k_conv's `eadd`).
 #pragma once
@@ -8,7 +8,6 @@
 #include <stdint.h>
 
 #include "tr_conv.h"
-#include "tr_conv_phase.h"
 
 namespace tr {
 
@@ -53,12 +52,5 @@ hipError_t launch_spectrum(const SpecPen& sp, const SpecBufs& b, const float* se
 // launch_spectrum into b.M, then the penalty value into b.val and d pen / d series into grad_out (rows, N)
 hipError_t launch_spectrum_penalty(const SpecPen& sp, const SpecBufs& b, const float* series, int64_t rows,
                                    float* grad_out, const int32_t* stop, hipStream_t st);
-hipError_t spectrum_prepare();
-// launch_update_conv_phase for the Fourier model: smoothness over [Kn | Ks (W, Rs*C)], the penalty
-// value (spec_val, nullptr: 0) between the L2 terms and the smoothness term
-hipError_t launch_update_conv_fourier(const FactorSet& fs, int n_bias, const float lam[4], const PhaseSmooth& sm, int W,
-                                      int Rn, int RsC, const float* spec_val, float* params, const float* grad,
-                                      const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
-                                      float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st);
 
 }  // namespace tr

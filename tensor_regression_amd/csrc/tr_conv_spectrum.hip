@@ -1,6 +1,7 @@
 // tr_conv_spectrum.hip — the output-spectrum penalty of the convolutional Fourier model
 // (convolutional_fourier_tensor_regression.py: spectral_penalty 727-812, set up at 1040-1048 and
-// 1260-1261; loss 1269-1282) and that model's update step.
+// 1260-1261; loss 1269-1282).  The model's update step is k_update_conv (tr_conv.hip), which adds
+// this penalty's value (SpecBufs::val) into the total.
 //
 //   C[k,n] = sum_{t<rows} x[t,n] cos(2 pi k t / n_fft),  S[k,n] = sum_t x[t,n] sin(2 pi k t / n_fft)
 //            (Y = rfft(x, n_fft) = C - i S; the series is zero-padded from rows to n_fft)     k < F
@@ -26,9 +27,6 @@
 //   k_spec_smooth / k_spec_pen / k_spec_val / k_spec_back   the terms between the two DFT passes, one
 //                thread per element, every sum in ascending index order; the mean's partials are fp64
 //                (one per workgroup, added in index order), the value is fp32(mean) * lambda_sp.
-//   k_update_conv_fourier   k_update_conv_phase (tr_conv_phase.hip) restated for this model: the
-//                smoothness term over [Kn | Ks] with Ks seen as (W, Rs C) (up to (257 + 8) x 64: dynamic
-//                LDS), total = (((rec + L2_w) + L2_n) + spec) + smooth, stops through k_converge_tail.
 // No float atomics; two runs on the same inputs are bitwise equal.  Every kernel returns at once when
 // the device stop flag is set.
 // Bounds: a thread with a >= A computes index 0 and stores nothing; tile rows >= the split's end are
@@ -217,152 +215,10 @@ __global__ __launch_bounds__(256) void k_spec_back(int64_t F, int64_t Fs, int N,
   im[e] *= f;
 }
 
-// k_update_conv_phase restated for the Fourier model (see the header comment); the reference's sum is
-//   loss_rec + L2(Bcp_w) + L2(Bcp_n) + loss_spectral + loss_smoothness          (…py:1281)
-struct FourierLam {
-  float v[4];  // by arena factor: Bd, Bo, Kn, Ks
-};
-
-__global__ __launch_bounds__(1024) void k_update_conv_fourier(FactorSet fs, int n_bias, FourierLam lam, PhaseSmooth sm,
-                                                              int W, int Rn, int RsC,
-                                                              const float* __restrict__ spec_val,
-                                                              float* __restrict__ params,
-                                                              const float* __restrict__ grad, UpdateArgs ua,
-                                                              float* __restrict__ m, float* __restrict__ v,
-                                                              float* __restrict__ vmax,
-                                                              float* __restrict__ grad_total_out,
-                                                              float* __restrict__ loss_out,
-                                                              double* __restrict__ loss_hist,
-                                                              int32_t* __restrict__ stop) {
-#pragma clang fp contract(off)
-  __shared__ float wsum[4 * 16];
-  __shared__ float norms[4];
-  __shared__ float coef[4];
-  __shared__ float ssum[2 * 16];
-  __shared__ float sval[2];
-  extern __shared__ float sd[];  // Delta^q of [Kn | Ks], (W + q) x (Rn + Rs C)
-  const int t = threadIdx.x, lane = t & 63, q = t >> 6;
-  const int64_t nfe = fs.nfelem, np = nfe + n_bias;
-  const bool checked = ua.mode == 0 && stop != nullptr;
-  const int32_t stop0 = stop != nullptr ? *stop : 0;
-  const float status = checked ? grad[np + 1] : 0.f;
-  auto factor_of = [&](int64_t e) {
-    int f = 0;
-#pragma unroll
-    for (int g = 1; g < 4; ++g)
-      if (e >= fs.off[g]) f = g;
-    return f;
-  };
-  float accn[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int64_t k = t; k < nfe; k += 1024) {
-    const float a = params[k];
-    const int f = factor_of(k);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
-  }
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    const float r = tr_wave_allreduce(accn[f]);
-    if (lane == 0) wsum[f * 16 + q] = r;
-  }
-  // Delta^q of the raw kernels and the two sums of its squares
-  const int ord = sm.order, Wq = W + ord, Rk = Rn + RsC;
-  float accs[2] = {0.f, 0.f};
-  for (int idx = t; idx < Wq * Rk; idx += 1024) {
-    const int i = idx / Rk, c = idx - i * Rk;
-    const float* col = c < Rn ? params + fs.off[2] + c : params + fs.off[3] + (c - Rn);
-    const int ld = c < Rn ? Rn : RsC;
-    float d = 0.f;
-    for (int j = 0; j <= ord; ++j) {
-      const int w = i - j;
-      if (w >= 0 && w < W) d = d + sm.c[j] * col[(int64_t)w * ld];
-    }
-    sd[idx] = d;
-    if (c < Rn)
-      accs[0] = fmaf(d, d, accs[0]);
-    else
-      accs[1] = fmaf(d, d, accs[1]);
-  }
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    const float r = tr_wave_allreduce(accs[f]);
-    if (lane == 0) ssum[f * 16 + q] = r;
-  }
-  __syncthreads();
-  if (t < 4) {
-    float tot = 0.f;
-    for (int w = 0; w < 16; ++w) tot += wsum[t * 16 + w];
-    norms[t] = sqrtf(tot);
-    coef[t] = lam.v[t] / (2.0f * norms[t]);
-  } else if (t >= 64 && t < 66) {
-    const int f = t - 64;
-    float tot = 0.f;
-    for (int w = 0; w < 16; ++w) tot += ssum[f * 16 + w];
-    const int rf = f == 0 ? Rn : RsC;
-    sval[f] = rf > 0 ? (tot / (float)(Wq * rf)) * sm.lam : 0.f;  // torch.mean(...) * lambda_smooth
-  }
-  __syncthreads();
-  if (stop0 != 0) return;
-  if (checked && status != 0.0f) {
-    if (t == 0) *stop = TR_STOP_DEVICE_ERROR - (int32_t)ua.iter;
-    return;
-  }
-  const bool adam = ua.mode != 1;
-  const bool ams = adam && ua.amsgrad;
-  for (int64_t e = t; e < np; e += 1024) {
-    float g = grad[e], p = params[e];
-    if (e < nfe) {
-      const int f = factor_of(e);
-      g = g + coef[f] * (2.0f * p);
-      if (f >= 2) {
-        const int rf = f == 2 ? Rn : RsC;
-        const int le = (int)(e - fs.off[f]);
-        const int w = le / rf, c = (f == 2 ? 0 : Rn) + (le - w * rf);
-        float gs = 0.f;
-        for (int j = 0; j <= ord; ++j) gs = gs + sm.c[j] * sd[(w + j) * Rk + c];
-        g = g + (2.0f * sm.lam / (float)(Wq * rf)) * gs;
-      }
-    }
-    if (!adam) {
-      grad_total_out[e] = g;
-      continue;
-    }
-    float mm = m[e], vv = v[e], vm = ams ? vmax[e] : 0.f;
-    g = ua.weight_decay != 0.0f ? fmaf(p, ua.weight_decay, g) : g;
-    mm = fmaf(ua.one_minus_b1, g - mm, mm);
-    vv = vv * ua.beta2;
-    vv = vv + ua.one_minus_b2 * g * g;
-    vm = fmaxf(vm, vv);
-    if (ams) vmax[e] = vm;
-    const float denom = sqrtf(ams ? vm : vv) / ua.bc2_sqrt + ua.eps;
-    p = p + (-ua.step_size) * (mm / denom);
-    m[e] = mm;
-    v[e] = vv;
-    params[e] = p;
-  }
-  if (t == 0) {
-    const float pw = (0.f + norms[2] * lam.v[2]) + norms[3] * lam.v[3];
-    const float pn = (0.f + norms[0] * lam.v[0]) + norms[1] * lam.v[1];
-    const float spec = spec_val != nullptr ? *spec_val : 0.f;
-    float ps = 0.f;  // an empty factor is skipped (comp.numel() > 0, …py:875)
-    if (Rn > 0) ps = ps + sval[0];
-    if (RsC > 0) ps = ps + sval[1];
-    const float total = (((grad[np] + pw) + pn) + spec) + ps;
-    if (loss_out != nullptr) *loss_out = total;
-    if (ua.mode == 0 && loss_hist != nullptr) loss_hist[ua.hist_base + ua.iter] = (double)total;
-    // the reference tests the plateau once len(loss_running) > patience, else the NaN stop (…py:1313-1320)
-    if (ua.mode == 0 && ua.nan_stop && stop != nullptr && ua.hist_base + ua.iter + 1 <= ua.patience &&
-        __builtin_isnan(total))
-      *stop = -(int32_t)(ua.iter + 1);
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
 namespace {
-constexpr size_t UPD_LDS_MAX = (size_t)(CONV_MAXW + PHASE_MAXQ) * CONV_MAXK * 4;
-
 // splits of the summation range and rows per split (a multiple of the tile)
 void dft_split(int64_t A, int64_t B, int N, int* nsplit, int64_t* bper) {
   const int64_t wg = ((A + DFT_T - 1) / DFT_T) * ((N + DFT_NC - 1) / DFT_NC);
@@ -459,31 +315,6 @@ hipError_t launch_spectrum_penalty(const SpecPen& sp, const SpecBufs& b, const f
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   return launch_dft<1>(sp, b, rows, sp.F, b.re, b.im, grad_out, nullptr, nullptr, stop, st);
-}
-
-hipError_t spectrum_prepare() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_update_conv_fourier),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)UPD_LDS_MAX);
-}
-
-hipError_t launch_update_conv_fourier(const FactorSet& fs, int n_bias, const float lam[4], const PhaseSmooth& sm, int W,
-                                      int Rn, int RsC, const float* spec_val, float* params, const float* grad,
-                                      const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
-                                      float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st) {
-  if (fs.nf != 4 || sm.order < 0 || sm.order > PHASE_MAXQ || W > CONV_MAXW || Rn + RsC > CONV_MAXK)
-    return hipErrorInvalidValue;
-  FourierLam l;
-  for (int i = 0; i < 4; ++i) l.v[i] = lam[i];
-  const size_t lds = (size_t)(W + sm.order) * (Rn + RsC) * 4;
-  hipLaunchKernelGGL(k_update_conv_fourier, dim3(1), dim3(1024), lds, st, fs, n_bias, l, sm, W, Rn, RsC, spec_val,
-                     params, grad, ua, m, v, vmax, grad_total_out, loss_out, loss_hist, stop);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const int64_t n_losses = ua.hist_base + ua.iter + 1;
-  if (ua.mode == 0 && loss_hist != nullptr && stop != nullptr && ua.patience >= 0 && n_losses > ua.patience &&
-      ua.tol > 0.0)
-    e = launch_converge_tail(loss_hist, n_losses, ua.iter, ua.patience, ua.tol, stop, st);
-  return e;
 }
 
 }  // namespace tr

@@ -1,6 +1,6 @@
 """GPU checks of the convolutional Fourier model (tensor_regression_amd.
-convolutional_fourier_tensor_regression; the spectrum path k_dft / k_spec_* and k_update_conv_fourier
-of csrc/tr_conv_spectrum.hip around k_conv of csrc/tr_conv.hip).
+convolutional_fourier_tensor_regression; the spectrum path k_dft / k_spec_* of
+csrc/tr_conv_spectrum.hip around k_conv and k_update_conv of csrc/tr_conv.hip).
 
   * fixture parity (tests/golden/cfs_*.npz, written by the reference) through the public class:
     y_hat0, the data loss, the penalty value, d pen / d y_hat, y_spectrum, every gradient (total and

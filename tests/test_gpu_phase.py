@@ -1,6 +1,6 @@
 """GPU checks of the phase-constrained spectral convolutional model (tensor_regression_amd.
-phase_constrained_spectral_convolutional_tensor_regression; kernels k_phase_kp, k_phase_finish and
-k_update_conv_phase in csrc/tr_conv_phase.hip around k_conv of csrc/tr_conv.hip).
+phase_constrained_spectral_convolutional_tensor_regression; kernels k_phase_kp and k_phase_finish
+in csrc/tr_conv_phase.hip around k_conv and k_update_conv of csrc/tr_conv.hip).
 
   * fixture parity (tests/golden/pcs_*.npz, written by the reference) through the public class:
     y_hat0, loss0, every gradient (total and data term alone), the 10-step and full loss

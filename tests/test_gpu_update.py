@@ -1,5 +1,6 @@
 """GPU checks of the update step: tr_finalize_grad / tr_adam_step called directly with chosen inputs
-(k_update, k64_update, k_update_conv, k_update_conv_phase; k_converge and k_converge_tail behind them).
+(k_update, k64_update, and both instantiations of k_update_conv, the one update kernel of the conv,
+phase and Fourier plans; k_converge and k_converge_tail behind them).
 
 No X is ever passed: the test writes the gradient arena itself (random data gradients, the data loss,
 the status slot) and reads back parameters, Adam state, loss history and stop flag.
@@ -21,8 +22,10 @@ the status slot) and reads back parameters, Adam state, loss history and stop fl
   * the plateau sum on the device against np.sum(np.abs(np.diff(...))) at tol = d and nextafter(d),
     at lengths on both sides of every branch of numpy's pairwise order; k_converge_tail's slices
 
-Conv and phase plans need max_series_rows >= the temporal window, so they are created with
-max_rows = W; every other plan with max_rows = 1.  With hist_base = 37 the plateau lengths below 37
+Conv, phase and Fourier plans need max_series_rows >= the temporal window, so they are created with
+max_rows = W; every other plan with max_rows = 1.  The Fourier cases run with the spectrum penalty off
+(its value in the total is covered by the cfs_* fixtures of test_gpu_fourier.py).  A phase plan and a
+Fourier plan with one component are the same update and must agree bitwise.  With hist_base = 37 the plateau lengths below 37
 do not exist (the patience would be negative) and are run at hist_base = 0 only.
 
 Largest measured e / e_torch of the same case, per plan family (MI355X; printed by every case with -s):
@@ -89,15 +92,28 @@ ARENAS = {
     "f64_1025": ("f64", ((64, 64), 8), 1025),
     "f64_2049": ("f64", ((128, 128), 8), 2049),
     "f64_7modes": ("f64", ((3, 5, 2, 7, 4, 6, 9), 37), 1333),
+    # (W, D, N, Rn, Rs, C, q); appended: a case's index seeds its inputs
+    "fourier_c2_q0": ("fourier", (65, 300, 4, 3, 3, 2, 0), 2413),
+    "fourier_c2_q2": ("fourier", (65, 300, 4, 3, 3, 2, 2), 2413),
+    "fourier_c2_q8": ("fourier", (65, 300, 4, 3, 3, 2, 8), 2413),
+    "fourier_rn0_q2": ("fourier", (9, 400, 2, 0, 3, 2, 2), 9 * 6 + 400 * 3 + 2 * 3 + 2),
 }
 # one small and one > 1024 arena per plan kind for the stop rules
 STOP_ARENAS = ["lin_17", "lin_2049", "mnl_small", "mnl_8factors", "spec_small", "spec_2831", "conv_small",
-               "conv_2413", "phase_small", "phase_2218_q2", "f64_small", "f64_2049"]
+               "conv_2413", "phase_small", "phase_2218_q2", "fourier_small", "fourier_c2_q2", "f64_small", "f64_2049"]
 ARENAS_EXTRA = {
     "mnl_small": ("multinomial", ((5, 3), 4, 2), 24),
     "conv_small": ("conv", (9, 5, 2, 1, 1, 2), 5 * 2 + 2 * 2 + 9 + 18 + 2),
     "phase_small": ("phase", (9, 5, 2, 1, 1, 2), 5 * 2 + 2 * 2 + 9 + 9 + 2),
+    "fourier_small": ("fourier", (9, 5, 2, 1, 1, 2, 2), 5 * 2 + 2 * 2 + 9 + 18 + 2),
+    "fourier_c1_q2": ("fourier", (65, 300, 4, 3, 3, 1, 2), 2218),  # phase_2218_q2's arena
     "f64_small": ("f64", ((5, 3), 2), 17),
+}
+# the largest Delta^q scratch of each family, 265 x 32 and 265 x 64 floats (67,840 B: past 64 KiB); one
+# hyperparameter set each
+LDS_MAX = {
+    "phase_lds_max": ("phase", (257, 3, 1, 16, 16, 8), 3 * 32 + 32 + 257 * 16 + 257 * 16 + 1),
+    "fourier_lds_max": ("fourier", (257, 3, 1, 0, 16, 4, 8), 3 * 16 + 16 + 257 * 64 + 1),
 }
 LAM_L2 = 0.03
 LAM_CONV = (0.02, 0.05, 0.11)  # (w, d, out)
@@ -109,7 +125,7 @@ class Arena:
 
     def __init__(self, name, flags=False):
         from tensor_regression_amd import _engine, _lib
-        kind, a, total = {**ARENAS, **ARENAS_EXTRA}[name]
+        kind, a, total = {**ARENAS, **ARENAS_EXTRA, **LDS_MAX}[name]
         self.name, self.kind = name, kind
         self.smooth = None
         if kind in ("linear", "f64", "multinomial"):
@@ -130,10 +146,14 @@ class Arena:
             elif kind == "conv":
                 self.plan = _engine.ConvPlan(*a, a[0], nn, None, DEV)
                 self.lam, pk = LAM_CONV, "conv"
-            else:
+            elif kind == "phase":
                 self.smooth = (LAM_SMOOTH, a[5])
                 self.plan = _engine.ConvPhasePlan(*a[:5], a[0], nn, None, DEV, *self.smooth)
                 self.lam, pk = LAM_CONV, "phase"
+            else:
+                self.smooth = (LAM_SMOOTH, a[6])
+                self.plan = _engine.ConvFourierPlan(*a[:6], a[0], nn, None, DEV, *self.smooth)
+                self.lam, pk = LAM_CONV, "fourier"
             self.n_bias = a[2]
         p = self.plan
         self.shapes = [tuple(s) for s in p.factor_shapes()]
@@ -153,7 +173,7 @@ class Arena:
     def penalty(self, lam=None, smooth=None):
         lam = self.lam if lam is None else lam
         sm = self.smooth if smooth is None else smooth
-        if self.kind in ("conv", "phase"):
+        if self.kind in ("conv", "phase", "fourier"):
             return ur.make_penalty(self.kind, self.off, self.shapes, list(lam), *(sm or ()))
         return ur.make_penalty("l2", self.off, self.shapes, lam)
 
@@ -175,9 +195,13 @@ def test_layouts_hit_the_intended_boundaries():
     assert len(a.shapes) == 8 and a.n_bias == 0    # TR_MAXF
     a = arena_of("spec_2831")
     assert a.n_bias == 5 and a.nfe == 2826
-    for n in ("conv_rn0", "conv_rs0", "phase_rn0_q2"):
+    for n in ("conv_rn0", "conv_rs0", "phase_rn0_q2", "fourier_rn0_q2"):
         a = arena_of(n)
         assert a.np > 1024 and any(int(np.prod(s)) == 0 for s in a.shapes)
+    assert arena_of("fourier_c2_q2").np > 2048     # past two trips of the 1024-thread loop
+    for n, cols in (("phase_lds_max", 32), ("fourier_lds_max", 64)):  # Delta^q: (W + q) x (Rn + RsK) floats
+        a = arena_of(n)
+        assert (a.shapes[2][0] + a.smooth[1]) * int(np.prod(a.shapes[2][1:]) + np.prod(a.shapes[3][1:])) == 265 * cols
 
 
 # ---- synthetic inputs ----------------------------------------------------------------------
@@ -337,7 +361,37 @@ def test_step_parity(name, hpset):
         run_case(a, rng, hp, t, hist_base=(0, 4)[j % 2], it=(0, 3, 1)[j % 3], with_finalize=(j == 0), twin=twin)
 
 
-CHAIN = ["lin_2049", "mnl_8factors", "spec_2831", "conv_2413", "phase_2218_q2", "f64_2049"]
+@pytest.mark.parametrize("name", list(LDS_MAX))
+def test_step_parity_at_the_largest_smoothness_scratch(name):
+    a = arena_of(name)
+    run_case(a, np.random.default_rng(4000 + list(LDS_MAX).index(name)), HP[2], 7, hist_base=4, it=3,
+             with_finalize=True)
+
+
+def test_phase_and_one_component_fourier_agree_bitwise():
+    """The phase plan and the Fourier plan with C = 1 have the same arena and the same update: one kernel,
+    the same arguments.  Same bytes in, same bytes out, for the Adam step and for finalize_grad."""
+    ph, fo = arena_of("phase_2218_q2"), arena_of("fourier_c1_q2")
+    assert ph.off == fo.off and ph.np == fo.np and ph.smooth == fo.smooth and ph.lam == fo.lam
+    hp = HP[2]
+    inp = make_inputs(ph, np.random.default_rng(91), zero_state=False, hp=hp)
+    out = []
+    for a in (ph, fo):
+        d = to_dev(inp)
+        hist, stop = new_hist(8), new_stop()
+        dev_step(a, d, hp, 7, hist, 4, 1, stop=stop)
+        d2 = to_dev(inp)
+        gtot = torch.full((a.np,), float("nan"), device=DEV)
+        loss = torch.full((1,), float("nan"), device=DEV)
+        a.plan.finalize_grad(d2["params"], d2["grad"], a.lam, gtot, loss)
+        out.append(dict(params=d["params"], m=d["m"], v=d["v"], vmax=d["vmax"], hist=hist, stop=stop, gtot=gtot,
+                        loss=loss))
+    assert not same_bits(out[0]["params"], inp["params"]) and np.isfinite(out[0]["hist"][5].item())
+    for k in out[0]:
+        assert same_bits(out[0][k], out[1][k]), k
+
+
+CHAIN = ["lin_2049", "mnl_8factors", "spec_2831", "conv_2413", "phase_2218_q2", "f64_2049", "fourier_c2_q2"]
 
 
 @pytest.mark.parametrize("name", CHAIN)
@@ -461,7 +515,7 @@ def test_nan_data_loss(name):
             assert _nan_step(a, hp, inp, hb, 0, pat) == -1
             assert _nan_step(a, hp, inp, hb, pat, pat) == -(pat + 1)
             assert _nan_step(a, hp, inp, hb, pat + 1, pat) == 0
-    else:                                           # phase: hist_base + iter + 1 <= patience
+    else:                                           # phase, Fourier: hist_base + iter + 1 <= patience
         assert _nan_step(a, hp, inp, 0, pat - 1, pat) == -pat
         assert _nan_step(a, hp, inp, 0, pat, pat) == 0
         assert _nan_step(a, hp, inp, 4, 1, pat) == -2
@@ -538,12 +592,12 @@ class _Plateau:
                    m=np.zeros(a.np, a.npdt), v=np.zeros(a.np, a.npdt), vmax=np.zeros(a.np, a.npdt))
         self.d = to_dev(inp)
         self.params0 = inp["params"]
-        self.lam = (0.0, 0.0, 0.0) if a.kind in ("conv", "phase") else 0.0
-        if a.kind == "phase":
+        self.lam = (0.0, 0.0, 0.0) if a.kind in ("conv", "phase", "fourier") else 0.0
+        if a.kind in ("phase", "fourier"):
             a.plan.set_smoothness(0.0, 2)
 
     def close(self):
-        if self.a.kind == "phase":
+        if self.a.kind in ("phase", "fourier"):
             self.a.plan.set_smoothness(*self.a.smooth)
 
     def flag(self, h, hist_base, it, patience, tol):

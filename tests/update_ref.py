@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 import conv_ref
+import fourier_ref
 import phase_ref
 
 # Adam hyperparameters in the form of tensor_regression_amd._engine.adam_hparams
@@ -31,7 +32,9 @@ def make_penalty(kind, offsets, shapes, lam, lam_smooth=0.0, order=2):
     """penalty(arena) -> scalar tensor in arena's dtype.
     kind "l2":    lam * sum_f sqrt(sum(A_f^2)) over the raw factors (linear, multinomial, spectral, f64)
     kind "conv":  conv_ref.penalty with lam = (w, d, out); arena order Bd | Bo | Kn | Ks
-    kind "phase": phase_ref.penalty + phase_ref.smoothness(lam_smooth, order); same arena order"""
+    kind "phase": phase_ref.penalty + phase_ref.smoothness(lam_smooth, order); same arena order
+    kind "fourier": conv_ref.penalty + fourier_ref.smoothness (Ks (W, Rs, C) seen as (W, Rs C)); same arena
+                  order; the spectrum penalty is off"""
     def penalty(arena):
         A = factors_of(arena, offsets, shapes)
         if kind == "l2":
@@ -44,6 +47,8 @@ def make_penalty(kind, offsets, shapes, lam, lam_smooth=0.0, order=2):
             return conv_ref.penalty(Kn, Ks, Bd, Bo, lam)
         if kind == "phase":
             return phase_ref.penalty(Kn, Ks, Bd, Bo, lam) + phase_ref.smoothness(Kn, Ks, lam_smooth, order)
+        if kind == "fourier":
+            return conv_ref.penalty(Kn, Ks, Bd, Bo, lam) + fourier_ref.smoothness(Kn, Ks, lam_smooth, order)
         raise ValueError(kind)
     return penalty
 
