@@ -12,6 +12,7 @@ import ctypes
 import math
 import os
 import sys
+import types
 import weakref
 
 import numpy as np
@@ -1168,38 +1169,35 @@ def run_adam_fit(plan, X, target, class_weight, norm, arena, weights, lambda_L2,
     parameters (sync_replicas) and one all-reduce(sum) of the gradient arena — data gradients,
     data loss and the device status slot — runs between the local gradient and the Adam step.
     """
-    dev = plan.device_str
-    fdt = getattr(plan, "dtype", torch.float32)
     allreduce = None
     if process_group is not None:
         sync_replicas(arena, process_group, checked=arena_checked)
         allreduce = gradient_allreduce(process_group, getattr(plan, "dev", None))
-    grad, m, v, vmax, stop, tmp = fit_state(plan, fdt, hp["amsgrad"])
-    base = len(loss_running)
-    # every entry a reader touches is written first: the loop writes [base, base + n_run) and the
-    # plateau test (launched only when tol > 0) also reads the earlier losses, which are copied in
-    hist = torch.empty(base + max(int(max_iter), 0) + 1, dtype=torch.float64, device=dev)
-    if base and tol > 0:
-        hist[:base] = torch.tensor(loss_running, dtype=torch.float64)
-    if verbose_cb is not None:
-        sync_every = 1
+
+    def chunk(ii, n, s):
+        for it in range(ii, ii + n):
+            if verbose_cb is not None:
+                verbose_cb.before_step(arena)
+            loss_grad_any(plan, X, target, class_weight, norm, arena, weights, s.grad, stop=s.stop, tmp=s.tmp)
+            if allreduce is not None:
+                allreduce(s.grad)
+            plan.adam_step(arena, s.grad, s.m, s.v, s.vmax, lambda_L2, hp, it + 1, s.hist, s.base, it, patience, tol,
+                           s.stop)
+        return n
+
+    # the host sync of a chunk, with a watchdog on the peers (the all-reduce path only)
+    wait = allreduce.wait if isinstance(allreduce, RcclAllReduce) and allreduce.size > 1 else None
     # the loop changes the arena only through adam_step: let each step prepare the next
     # iteration's factors (one launch fewer per iteration, bitwise identical results)
     prep_next = _PREPARE_NEXT and isinstance(plan, Plan) and not isinstance(plan, SpectralPlan)
     if prep_next:
         plan.set_prepare_next(True)
     try:
-        ii, stopped_at = _adam_loop(plan, X, target, class_weight, norm, arena, weights, lambda_L2, max_iter, tol,
-                                    patience, hp, verbose_cb, allreduce, sync_every, grad, m, v, vmax, hist, base,
-                                    stop, tmp)
+        return _adam_loop(plan, getattr(plan, "dtype", torch.float32), hp, loss_running, max_iter, tol, verbose_cb,
+                          sync_every, chunk, wait)
     finally:
         if prep_next:
             plan.set_prepare_next(False)
-    # stop flag: > 0 plateau convergence after that many iterations; < 0 NaN stop (spectral)
-    n_run = abs(stopped_at) if stopped_at else ii
-    loss_running.extend(hist[base:base + n_run].tolist())
-    plan.last_stop = stopped_at
-    return stopped_at > 0, n_run
 
 
 def run_adam_fit_groups(plan, X, target, class_weight, norm, arena, weights, lambda_L2, max_iter, tol, patience,
@@ -1213,10 +1211,38 @@ def run_adam_fit_groups(plan, X, target, class_weight, norm, arena, weights, lam
     (Plan.set_resident) and each chunk of up to `sync_every` (<= 64) iterations is ONE launch, cut
     at the loop indices in `breaks` (where a learning rate changes: lr is constant per launch).
     Returns (convergence_reached, number_of_iterations_run)."""
-    dev = plan.device_str
-    grad, m, v, vmax, stop, tmp = fit_state(plan, torch.float32, hp["amsgrad"])
-    base = len(loss_running)
-    hist = torch.empty(base + max(int(max_iter), 0) + 1, dtype=torch.float64, device=dev)
+    def streamed(ii, n, s):
+        for it in range(ii, ii + n):
+            if verbose_cb is not None:
+                verbose_cb.before_step(arena)
+            loss_grad_any(plan, X, target, class_weight, norm, arena, weights, s.grad, stop=s.stop, tmp=s.tmp)
+            plan.adam_step_groups(arena, s.grad, s.m, s.v, s.vmax, lambda_L2, hp, lr_at(it), stepped, it + 1, s.hist,
+                                  s.base, it, patience, tol, s.stop)
+        return n
+
+    def one_launch(ii, n, s):
+        n = min([b - ii for b in breaks if ii < b < ii + n], default=n)
+        if verbose_cb is not None:  # then a chunk is one iteration
+            verbose_cb.before_step(arena)
+        plan.fit_resident(X, target, arena, weights, s.m, s.v, s.vmax, lambda_L2, hp, lr_at(ii), ii + 1, n, s.hist,
+                          s.base, ii, patience, tol, s.stop)
+        return n
+
+    return _adam_loop(plan, torch.float32, hp, loss_running, max_iter, tol, verbose_cb, sync_every,
+                      one_launch if resident else streamed)
+
+
+def _adam_loop(plan, fdt, hp, loss_running, max_iter, tol, verbose_cb, sync_every, chunk, wait=None):
+    """The chunked fit loop of run_adam_fit and run_adam_fit_groups: the fit state and the loss
+    history, one host sync per chunk, the resume after a failed pass, the verbose callback and the
+    epilogue.  `chunk(ii, n, s)` launches up to n iterations from loop index ii on the state `s`
+    (grad, m, v, vmax, stop, tmp, hist, base) and returns how many it launched."""
+    s = types.SimpleNamespace()
+    s.grad, s.m, s.v, s.vmax, s.stop, s.tmp = fit_state(plan, fdt, hp["amsgrad"])
+    s.base = base = len(loss_running)
+    # every entry a reader touches is written first: the loop writes [base, base + n_run) and the
+    # plateau test (launched only when tol > 0) also reads the earlier losses, which are copied in
+    s.hist = hist = torch.empty(base + max(int(max_iter), 0) + 1, dtype=torch.float64, device=plan.device_str)
     if base and tol > 0:
         hist[:base] = torch.tensor(loss_running, dtype=torch.float64)
     if verbose_cb is not None:
@@ -1224,62 +1250,17 @@ def run_adam_fit_groups(plan, X, target, class_weight, norm, arena, weights, lam
     ii = 0
     stopped_at = 0
     while ii < max_iter:
-        n = min(sync_every, max_iter - ii)
-        if resident:
-            nxt = [b for b in breaks if ii < b < ii + n]
-            if nxt:
-                n = min(nxt) - ii
-            plan.fit_resident(X, target, arena, weights, m, v, vmax, lambda_L2, hp, lr_at(ii), ii + 1, n, hist, base,
-                              ii, patience, tol, stop)
-        else:
-            for it in range(ii, ii + n):
-                loss_grad_any(plan, X, target, class_weight, norm, arena, weights, grad, stop=stop, tmp=tmp)
-                plan.adam_step_groups(arena, grad, m, v, vmax, lambda_L2, hp, lr_at(it), stepped, it + 1, hist, base,
-                                      it, patience, tol, stop)
-        ii += n
-        stopped_at = int(stop.item())  # one host sync per chunk
-        if stopped_at <= _lib.TR_STOP_DEVICE_ERROR:  # as in _adam_loop: resume that iteration on two passes
-            failed = _lib.TR_STOP_DEVICE_ERROR - stopped_at
-            plan.recover(f"iteration {failed}")
-            stop.zero_()
-            ii, stopped_at = failed, 0
-            continue
-        plan.check_status()
-        if verbose_cb is not None:
-            verbose_cb.after_step(ii - 1, float(hist[base + ii - 1].item()))
-        if stopped_at:
-            break
-    n_run = abs(stopped_at) if stopped_at else ii
-    loss_running.extend(hist[base:base + n_run].tolist())
-    plan.last_stop = stopped_at
-    return stopped_at > 0, n_run
-
-
-def _adam_loop(plan, X, target, class_weight, norm, arena, weights, lambda_L2, max_iter, tol, patience, hp,
-               verbose_cb, allreduce, sync_every, grad, m, v, vmax, hist, base, stop, tmp):
-    ii = 0
-    stopped_at = 0
-    while ii < max_iter:
-        n = min(sync_every, max_iter - ii)
-        for k in range(n):
-            it = ii + k
-            if verbose_cb is not None:
-                verbose_cb.before_step(arena)
-            loss_grad_any(plan, X, target, class_weight, norm, arena, weights, grad, stop=stop, tmp=tmp)
-            if allreduce is not None:
-                allreduce(grad)
-            plan.adam_step(arena, grad, m, v, vmax, lambda_L2, hp, it + 1, hist, base, it, patience, tol, stop)
-        ii += n
-        if isinstance(allreduce, RcclAllReduce) and allreduce.size > 1:
-            allreduce.wait()  # the host sync below, with a watchdog on the peers
-        stopped_at = int(stop.item())  # one host sync per chunk
+        ii += chunk(ii, min(sync_every, max_iter - ii), s)
+        if wait is not None:
+            wait()
+        stopped_at = int(s.stop.item())  # one host sync per chunk
         if stopped_at <= _lib.TR_STOP_DEVICE_ERROR:
             # a pass failed on the device (on any rank: the status slot is all-reduced with the
             # gradients, so every rank stops at the same iteration): nothing from that iteration on
             # was applied, so resume it on the two-pass path with the same parameters / Adam state
             failed = _lib.TR_STOP_DEVICE_ERROR - stopped_at
             plan.recover(f"iteration {failed}")
-            stop.zero_()
+            s.stop.zero_()
             ii, stopped_at = failed, 0
             continue
         plan.check_status()
@@ -1287,4 +1268,8 @@ def _adam_loop(plan, X, target, class_weight, norm, arena, weights, lambda_L2, m
             verbose_cb.after_step(ii - 1, float(hist[base + ii - 1].item()))
         if stopped_at:
             break
-    return ii, stopped_at
+    # stop flag: > 0 plateau convergence after that many iterations; < 0 NaN stop (spectral)
+    n_run = abs(stopped_at) if stopped_at else ii
+    loss_running.extend(hist[base:base + n_run].tolist())
+    plan.last_stop = stopped_at
+    return stopped_at > 0, n_run

@@ -33,6 +33,7 @@
 // beyond T are zero-filled and times >= T' contribute e = 0.
 #include <cstring>
 
+#include "tr_adam.h"
 #include "tr_conv.h"
 
 namespace tr {
@@ -366,7 +367,8 @@ __global__ __launch_bounds__(256) void k_conv_finish(int64_t nparams, int64_t nf
 }
 
 // The update of the three convolutional models (conv spectral, phase-constrained, Fourier): k_update's
-// arithmetic (tr_update.hip) with one lambda per factor and the reference's order of the penalty sum,
+// norms, prologue and Adam step (tr_adam.h) with one lambda per factor, a fixed nf = 4, one element per
+// trip, and the reference's order of the penalty sum,
 //   loss + L2_penalty(Bcp_w, [l0, l0]) + L2_penalty(Bcp_n, l[1:])                    (conv …py:1046)
 //   ... + loss_spectral + loss_smoothness                                 (phase …py:1412, Fourier …py:1281)
 // A kernel of its own: k_update as compiled for the other models is untouched.
@@ -400,23 +402,9 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
   extern __shared__ float sd[];  // Delta^q of [Kn | Ks], (W + q) x (Rn + RsK)
   const int t = threadIdx.x, lane = t & 63, q = t >> 6;
   const int64_t nfe = fs.nfelem, np = nfe + n_bias;
-  const bool checked = ua.mode == 0 && stop != nullptr;
-  const int32_t stop0 = stop != nullptr ? *stop : 0;
-  const float status = checked ? grad[np + 1] : 0.f;
-  auto factor_of = [&](int64_t e) {
-    int f = 0;
-#pragma unroll
-    for (int g = 1; g < 4; ++g)
-      if (e >= fs.off[g]) f = g;
-    return f;
-  };
-  float accn[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int64_t k = t; k < nfe; k += 1024) {
-    const float a = params[k];
-    const int f = factor_of(k);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
-  }
+  const StopState ss = stop_load(stop, ua.mode == 0, grad, np);
+  float accn[TR_MAXF] = {};
+  for (int64_t k = t; k < nfe; k += 1024) norm_add(fs, 4, k, params[k], accn);
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     const float r = tr_wave_allreduce(accn[f]);
@@ -449,10 +437,7 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
   }
   __syncthreads();
   if (t < 4) {
-    float tot = 0.f;
-    for (int w = 0; w < 16; ++w) tot += wsum[t * 16 + w];
-    norms[t] = sqrtf(tot);
-    coef[t] = lam.v[t] / (2.0f * norms[t]);
+    norm_finish<16>(wsum, t, lam.v[t], norms, coef);
   } else if (SMOOTH && t >= 64 && t < 66) {
     const int f = t - 64;
     float tot = 0.f;
@@ -461,17 +446,13 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
     sval[f] = rf > 0 ? (tot / (float)(Wq * rf)) * sm.lam : 0.f;  // torch.mean(...) * lambda_smooth
   }
   __syncthreads();
-  if (stop0 != 0) return;
-  if (checked && status != 0.0f) {
-    if (t == 0) *stop = TR_STOP_DEVICE_ERROR - (int32_t)ua.iter;
-    return;
-  }
+  if (stop_taken(ss, stop, ua.iter, t)) return;
   const bool adam = ua.mode != 1;
   const bool ams = adam && ua.amsgrad;
   for (int64_t e = t; e < np; e += 1024) {
     float g = grad[e], p = params[e];
     if (e < nfe) {
-      const int f = factor_of(e);
+      const int f = factor_of(fs, 4, e);
       g = g + coef[f] * (2.0f * p);
       if (SMOOTH && f >= 2) {
         const int rf = f == 2 ? Rn : RsK;
@@ -487,14 +468,10 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
       continue;
     }
     float mm = m[e], vv = v[e], vm = ams ? vmax[e] : 0.f;
-    g = ua.weight_decay != 0.0f ? fmaf(p, ua.weight_decay, g) : g;
-    mm = fmaf(ua.one_minus_b1, g - mm, mm);
-    vv = vv * ua.beta2;
-    vv = vv + ua.one_minus_b2 * g * g;
+    adam_moments(p, g, mm, vv, ua.weight_decay, ua.one_minus_b1, ua.beta2, ua.one_minus_b2);
     vm = fmaxf(vm, vv);
     if (ams) vmax[e] = vm;
-    const float denom = sqrtf(ams ? vm : vv) / ua.bc2_sqrt + ua.eps;
-    p = p + (-ua.step_size) * (mm / denom);
+    p = adam_param(p, mm, ams ? vm : vv, ua.bc2_sqrt, ua.eps, ua.step_size);
     m[e] = mm;
     v[e] = vv;
     params[e] = p;

@@ -297,6 +297,7 @@ __global__ __launch_bounds__(1024) void k64_update(FactorSet fs, int n_bias, dou
       grad_total_out[e] = g;
       continue;
     }
+    // not tr_adam.h's helpers: this kernel is compiled with contraction on (vv + (1 - b2) g g may fuse)
     if (ua.weight_decay != 0.0) g = fma(p, ua.weight_decay, g);
     double mm = m[e];
     mm = fma(ua.one_minus_b1, g - mm, mm);

@@ -115,7 +115,7 @@ hipError_t launch_update(const FactorSet& fs, int n_bias, float* params, const f
                          const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
                          float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st,
                          const PrepArgs* prep = nullptr);
-// Per-factor scalars of one k_update_groups launch (torch.optim.Adam with one param group per
+// Per-factor scalars of one k_update<true> launch (torch.optim.Adam with one param group per
 // factor): step_size[f] = lr_f / (1 - b1^t) rounded to fp32 like UpdateArgs::step_size; bit f of
 // mask set = factor f is in a param group (stepped), clear = left bitwise untouched.
 struct GroupArgs {

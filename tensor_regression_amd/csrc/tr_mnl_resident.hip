@@ -18,7 +18,7 @@
 //                                                                      p; the S splits added in order)
 //   6  the three factor gradients from G with the softplus chain (thread per parameter);
 //      ||A_f|| of the raw factors (one wave per factor)
-//   7  L2 term + torch's _single_tensor_adam, one step size per factor (k_update_groups' arithmetic)
+//   7  L2 term + torch's _single_tensor_adam, one step size per factor (k_update<true>'s arithmetic, tr_adam.h)
 //   8  thread 0: loss_hist[hist_base + iter] = data + lambda sum ||A_f||, then the plateau test by
 //      np_pairwise_sum_absdiff (k_converge's) into one LDS word
 // and after that barrier every thread reads the word, so all leave the loop together.
@@ -32,6 +32,7 @@
 // for the same reason; B and dZ are read at wave-uniform addresses (broadcast).
 #include "tr_mnl_resident.h"
 
+#include "tr_adam.h"
 #include "tr_common.h"
 #include "tr_np_sum.h"
 
@@ -263,17 +264,13 @@ __global__ __launch_bounds__(RES_T) void k_mnl_resident(ResArgs a, const float* 
       float p = sPar[e];
       float gr = sGrad[e] + sNorm[4 + f] * (2.0f * p);
       float mm = sM[e], vv = sV[e];
-      gr = a.weight_decay != 0.0f ? fmaf(p, a.weight_decay, gr) : gr;  // grad.add(param, alpha=wd)
-      mm = fmaf(a.one_minus_b1, gr - mm, mm);                            // exp_avg.lerp_(grad, 1 - b1)
-      vv = vv * a.beta2;                                                 // exp_avg_sq.mul_(b2)
-      vv = vv + a.one_minus_b2 * gr * gr;                                //   .addcmul_(g, g, 1 - b2)
+      adam_moments(p, gr, mm, vv, a.weight_decay, a.one_minus_b1, a.beta2, a.one_minus_b2);
       float vm = 0.f;
       if (ams) {
         vm = fmaxf(sVm[e], vv);
         sVm[e] = vm;
       }
-      const float denom = sqrtf(ams ? vm : vv) / a.bc2_sqrt[it] + a.eps;
-      p = p + (-a.step_size[f][it]) * (mm / denom);                      // addcdiv_(m, denom, -step_size)
+      p = adam_param(p, mm, ams ? vm : vv, a.bc2_sqrt[it], a.eps, a.step_size[f][it]);
       sM[e] = mm;
       sV[e] = vv;
       sPar[e] = p;

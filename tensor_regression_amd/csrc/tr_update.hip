@@ -22,6 +22,7 @@
 // step, are bitwise those of the element-by-element loop.
 #include <cstring>
 
+#include "tr_adam.h"
 #include "tr_common.h"
 #include "tr_kernels.h"
 #include "tr_np_sum.h"  // np_pairwise_sum_absdiff (k_converge, k_converge_tail)
@@ -43,48 +44,45 @@ __device__ int g_upd_launch;
 namespace {
 constexpr int UPD_T = 1024;  // threads of the one workgroup (the norm order above assumes it)
 constexpr int UPD_TRIP = 2;  // elements per thread per loop trip (loads in flight together; 4: no better)
-
-__device__ __forceinline__ int factor_of(const FactorSet& fs, int64_t e) {
-  int f = 0;
-#pragma unroll
-  for (int g = 1; g < TR_MAXF; ++g)
-    if (g < fs.nf && e >= fs.off[g]) f = g;
-  return f;
-}
 }
 
+// GROUPS = true: torch.optim.Adam with one param group per factor
+// (multinomial_tensor_regression_hierarchical.py:436-440): every factor f has its own step size
+// lr_f / (1 - b1^t) (ga.step_size, read from LDS) and a stepped flag (ga.mask), all on one shared
+// step count t.  A factor outside the mask is a tensor the optimizer was never given: its gradient
+// (data + L2) exists and its norm enters the recorded loss, but its parameters and m / v / vmax are
+// never written (the two-element trip may load them: the buffers are arena-sized).  Adam only
+// (mode 0), no bias entries, no next-iteration preparation.  With every factor in the mask at one
+// lr the results are bitwise those of GROUPS = false.
+template <bool GROUPS>
 __global__ __launch_bounds__(UPD_T) void k_update(FactorSet fs, int n_bias,
                                                   float* __restrict__ params, const float* __restrict__ grad,
                                                   UpdateArgs ua, float* __restrict__ m, float* __restrict__ v,
                                                   float* __restrict__ vmax, float* __restrict__ grad_total_out,
                                                   float* __restrict__ loss_out, double* __restrict__ loss_hist,
-                                                  int32_t* __restrict__ stop, PrepArgs pa) {
+                                                  int32_t* __restrict__ stop, PrepArgs pa, GroupArgs ga) {
 #pragma clang fp contract(off)
   __shared__ float wsum[TR_MAXF * 16];
   __shared__ float norms[TR_MAXF];
   __shared__ float coef[TR_MAXF];
+  __shared__ float ssize[GROUPS ? TR_MAXF : 1];
   UPD_MARK(0);
   const int t = threadIdx.x;
   const int lane = t & (TR_WAVE - 1);
   const int q = t / TR_WAVE;
-  constexpr int NWV = UPD_T / TR_WAVE;
   constexpr int64_t B = UPD_T;
   const int64_t nfe = fs.nfelem;
-  const int64_t np = nfe + n_bias;  // bias entries after the factors (linear 1, spectral n_out)
-  // the flag and the status slot are loaded first and branched on after the norms
-  const bool checked = ua.mode == 0 && stop != nullptr;
-  const int32_t stop0 = stop != nullptr ? *stop : 0;
-  const float status = checked ? grad[np + 1] : 0.f;
-  // ||A_f||_F of every factor (raw parameters): per-thread sums in increasing k, the factor's
-  // accumulator selected without a branch, then the wave butterfly and the wave-order LDS sum
+  const int64_t np = GROUPS ? nfe : nfe + n_bias;  // bias entries after the factors (linear 1, spectral n_out)
+  // (stop_load and norm_add are called through a lambda, which the compiler inlines after it has
+  // simplified the body on its own: force-inlined straight into this kernel, at the SGPR ceiling,
+  // they cost it 3 to 16 instructions and up to 16 more lane reads)
+  const StopState ss = [&] { return stop_load(stop, ua.mode == 0, grad, np); }();
+  // ||A_f||_F of every factor (raw parameters): per-thread sums in increasing k, then the wave
+  // butterfly and the wave-order LDS sum
   float accn[TR_MAXF];
 #pragma unroll
   for (int f = 0; f < TR_MAXF; ++f) accn[f] = 0.f;
-  auto acc = [&](int64_t k, float a) {
-    const int f = factor_of(fs, k);
-#pragma unroll
-    for (int g = 0; g < TR_MAXF; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
-  };
+  auto acc = [&](int64_t k, float a) { norm_add(fs, fs.nf, k, a, accn); };
   int64_t k = t;
   for (; k + (UPD_TRIP - 1) * B < nfe; k += UPD_TRIP * B) {
     float a[UPD_TRIP];
@@ -104,45 +102,34 @@ __global__ __launch_bounds__(UPD_T) void k_update(FactorSet fs, int n_bias,
   UPD_MARK(1);
   __syncthreads();
   if (t < fs.nf) {
-    float tot = 0.f;
-    for (int w = 0; w < NWV; ++w) tot += wsum[t * 16 + w];
-    norms[t] = sqrtf(tot);
-    coef[t] = ua.lambda_l2 / (2.0f * norms[t]);  // d/dA lambda ||A|| = (lambda / (2 ||A||)) * (2 A)
+    norm_finish<UPD_T / TR_WAVE>(wsum, t, ua.lambda_l2, norms, coef);
+    if constexpr (GROUPS) ssize[t] = ga.step_size[t];
   }
   __syncthreads();
   UPD_MARK(2);
-  if (stop0 != 0) return;
-  // a failed pass (status slot set, summed over shards by the all-reduce): stop the fit before
-  // the step so the parameters and the Adam state stay those of the last good iteration
-  if (checked && status != 0.0f) {
-    if (t == 0) *stop = TR_STOP_DEVICE_ERROR - (int32_t)ua.iter;
-    return;
-  }
+  if (stop_taken(ss, stop, ua.iter, t)) return;
   unsigned nnmask = 0;  // factors under softplus (the next iteration's phi / dphi)
 #pragma unroll
   for (int g = 0; g < TR_MAXF; ++g)
     if (g < fs.nf && fs.nonneg[g]) nnmask |= 1u << g;
-  const bool adam = ua.mode != 1;
+  const bool adam = GROUPS || ua.mode != 1;
   const bool ams = adam && ua.amsgrad;
   auto step = [&](int64_t e, float g, float p, float mm, float vv, float vm) {
-    const int f = factor_of(fs, e);
+    const int f = factor_of(fs, fs.nf, e);
     g = e < nfe ? g + coef[f] * (2.0f * p) : g;
     if (!adam) {
       grad_total_out[e] = g;
       return;
     }
-    g = ua.weight_decay != 0.0f ? fmaf(p, ua.weight_decay, g) : g;  // grad.add(param, alpha=wd)
-    mm = fmaf(ua.one_minus_b1, g - mm, mm);                          // exp_avg.lerp_(grad, 1 - b1)
-    vv = vv * ua.beta2;                                              // exp_avg_sq.mul_(b2)
-    vv = vv + ua.one_minus_b2 * g * g;                               //   .addcmul_(g, g, 1 - b2)
+    if (GROUPS && !((ga.mask >> f) & 1u)) return;  // not in any param group: parameters and state untouched
+    adam_moments(p, g, mm, vv, ua.weight_decay, ua.one_minus_b1, ua.beta2, ua.one_minus_b2);
     vm = fmaxf(vm, vv);
     if (ams) vmax[e] = vm;
-    const float denom = sqrtf(ams ? vm : vv) / ua.bc2_sqrt + ua.eps;
-    p = p + (-ua.step_size) * (mm / denom);                          // addcdiv_(m, denom, -step_size)
+    p = adam_param(p, mm, ams ? vm : vv, ua.bc2_sqrt, ua.eps, GROUPS ? ssize[f] : ua.step_size);
     m[e] = mm;
     v[e] = vv;
     params[e] = p;
-    if (pa.mode > 0 && e < nfe) {  // the next iteration's phi / dphi (k_prep_factors' arithmetic)
+    if (!GROUPS && pa.mode > 0 && e < nfe) {  // the next iteration's phi / dphi (k_prep_factors' arithmetic)
       const bool soft = (nnmask >> f) & 1u;
       pa.phi[e] = soft ? tr_softplus(p, pa.beta, pa.thr) : p;
       pa.dphi[e] = soft ? tr_softplus_grad(p, pa.beta, pa.thr) : 1.0f;
@@ -170,11 +157,12 @@ __global__ __launch_bounds__(UPD_T) void k_update(FactorSet fs, int n_bias,
     float l2 = 0.f;
     for (int f = 0; f < fs.nf; ++f) l2 = l2 + norms[f];
     const float total = grad[np] + ua.lambda_l2 * l2;
-    if (loss_out != nullptr) *loss_out = total;
+    if (!GROUPS && loss_out != nullptr) *loss_out = total;
     if (ua.mode == 0 && loss_hist != nullptr) loss_hist[ua.hist_base + ua.iter] = (double)total;
     // spectral…py:738-741: `elif np.isnan(loss_running[-1])` only while ii <= patience;
     // a negative flag = stopped without convergence, |flag| iterations run
-    if (ua.mode == 0 && ua.nan_stop && stop != nullptr && ua.iter <= ua.patience && __builtin_isnan(total))
+    if (!GROUPS && ua.mode == 0 && ua.nan_stop && stop != nullptr && ua.iter <= ua.patience &&
+        __builtin_isnan(total))
       *stop = -(int32_t)(ua.iter + 1);
   }
   UPD_MARK(4);
@@ -495,16 +483,14 @@ bool update_prepare_mode_ok(const FactorSet& fs, int mode) {
   return mode <= 1;
 }
 
-hipError_t launch_update(const FactorSet& fs, int n_bias, float* params, const float* grad,
-                         const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
-                         float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st, const PrepArgs* pa) {
-  PrepArgs p0;
-  std::memset(&p0, 0, sizeof(p0));
-  const PrepArgs& pp = pa != nullptr && ua.mode == 0 ? *pa : p0;
-  if (!update_prepare_mode_ok(fs, pp.mode)) return hipErrorInvalidValue;
-  if (fs.nf < 1 || fs.nf > TR_MAXF) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_update, dim3(1), dim3(UPD_T), 0, st, fs, n_bias, params, grad, ua, m, v, vmax,
-                     grad_total_out, loss_out, loss_hist, stop, pp);
+// the step, then the plateau test when it can fire
+template <bool GROUPS>
+static hipError_t update_and_converge(const FactorSet& fs, int n_bias, float* params, const float* grad,
+                                      const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
+                                      float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st,
+                                      const PrepArgs& pa, const GroupArgs& ga) {
+  hipLaunchKernelGGL(k_update<GROUPS>, dim3(1), dim3(UPD_T), 0, st, fs, n_bias, params, grad, ua, m, v, vmax,
+                     grad_total_out, loss_out, loss_hist, stop, pa, ga);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (ua.mode == 0 && loss_hist != nullptr && stop != nullptr && ua.iter > ua.patience && ua.tol > 0.0) {
@@ -515,118 +501,28 @@ hipError_t launch_update(const FactorSet& fs, int n_bias, float* params, const f
   return e;
 }
 
-// ==========================================================================================
-// k_update restated for torch.optim.Adam with one param group per factor
-// (multinomial_tensor_regression_hierarchical.py:436-440): every factor f has its own step size
-// lr_f / (1 - b1^t) and a stepped flag.  A factor outside the mask is a tensor the optimizer was
-// never given: its gradient (data + L2) exists and its norm enters the recorded loss, but its
-// parameters and m / v / vmax are neither read for the step nor written.  Same norm order (thread
-// t sums the elements k = t (mod 1024) in increasing k, wave butterfly, wave-order LDS sum), same
-// _single_tensor_adam sequence and one shared step count t as k_update; with every factor in the
-// mask at one lr the results are bitwise k_update's.  Adam only (mode 0), no bias entries, no
-// next-iteration preparation.
-// ==========================================================================================
-__global__ __launch_bounds__(UPD_T) void k_update_groups(FactorSet fs, float* __restrict__ params,
-                                                         const float* __restrict__ grad, UpdateArgs ua,
-                                                         GroupArgs ga, float* __restrict__ m, float* __restrict__ v,
-                                                         float* __restrict__ vmax, double* __restrict__ loss_hist,
-                                                         int32_t* __restrict__ stop) {
-#pragma clang fp contract(off)
-  __shared__ float wsum[TR_MAXF * 16];
-  __shared__ float norms[TR_MAXF];
-  __shared__ float coef[TR_MAXF];
-  __shared__ float ssize[TR_MAXF];
-  const int t = threadIdx.x;
-  const int lane = t & (TR_WAVE - 1);
-  const int q = t / TR_WAVE;
-  constexpr int NWV = UPD_T / TR_WAVE;
-  constexpr int64_t B = UPD_T;
-  const int64_t np = fs.nfelem;
-  const bool checked = stop != nullptr;
-  const int32_t stop0 = stop != nullptr ? *stop : 0;
-  const float status = checked ? grad[np + 1] : 0.f;
-  float accn[TR_MAXF];
-#pragma unroll
-  for (int f = 0; f < TR_MAXF; ++f) accn[f] = 0.f;
-  auto acc = [&](int64_t k, float a) {
-    const int f = factor_of(fs, k);
-#pragma unroll
-    for (int g = 0; g < TR_MAXF; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
-  };
-  int64_t k = t;
-  for (; k + (UPD_TRIP - 1) * B < np; k += UPD_TRIP * B) {
-    float a[UPD_TRIP];
-#pragma unroll
-    for (int u = 0; u < UPD_TRIP; ++u) a[u] = params[k + u * B];
-#pragma unroll
-    for (int u = 0; u < UPD_TRIP; ++u) acc(k + u * B, a[u]);
-  }
-  for (; k < np; k += B) acc(k, params[k]);
-#pragma unroll
-  for (int f = 0; f < TR_MAXF; ++f) {
-    if (f < fs.nf) {
-      const float r = tr_wave_allreduce(accn[f]);
-      if (lane == 0) wsum[f * 16 + q] = r;
-    }
-  }
-  __syncthreads();
-  if (t < fs.nf) {
-    float tot = 0.f;
-    for (int w = 0; w < NWV; ++w) tot += wsum[t * 16 + w];
-    norms[t] = sqrtf(tot);
-    coef[t] = ua.lambda_l2 / (2.0f * norms[t]);
-    ssize[t] = ga.step_size[t];
-  }
-  __syncthreads();
-  if (stop0 != 0) return;
-  if (checked && status != 0.0f) {
-    if (t == 0) *stop = TR_STOP_DEVICE_ERROR - (int32_t)ua.iter;
-    return;
-  }
-  const bool ams = ua.amsgrad;
-  for (int64_t e = t; e < np; e += B) {
-    const int f = factor_of(fs, e);
-    if (!((ga.mask >> f) & 1u)) continue;  // not in any param group: parameters and state untouched
-    float p = params[e];
-    float g = grad[e] + coef[f] * (2.0f * p);
-    float mm = m[e], vv = v[e];
-    g = ua.weight_decay != 0.0f ? fmaf(p, ua.weight_decay, g) : g;  // grad.add(param, alpha=wd)
-    mm = fmaf(ua.one_minus_b1, g - mm, mm);                          // exp_avg.lerp_(grad, 1 - b1)
-    vv = vv * ua.beta2;                                              // exp_avg_sq.mul_(b2)
-    vv = vv + ua.one_minus_b2 * g * g;                               //   .addcmul_(g, g, 1 - b2)
-    float vm = 0.f;
-    if (ams) {
-      vm = fmaxf(vmax[e], vv);
-      vmax[e] = vm;
-    }
-    const float denom = sqrtf(ams ? vm : vv) / ua.bc2_sqrt + ua.eps;
-    p = p + (-ssize[f]) * (mm / denom);                              // addcdiv_(m, denom, -step_size)
-    m[e] = mm;
-    v[e] = vv;
-    params[e] = p;
-  }
-  if (t == 0) {
-    float l2 = 0.f;
-    for (int f = 0; f < fs.nf; ++f) l2 = l2 + norms[f];
-    const float total = grad[np] + ua.lambda_l2 * l2;
-    if (loss_hist != nullptr) loss_hist[ua.hist_base + ua.iter] = (double)total;
-  }
+hipError_t launch_update(const FactorSet& fs, int n_bias, float* params, const float* grad,
+                         const UpdateArgs& ua, float* m, float* v, float* vmax, float* grad_total_out,
+                         float* loss_out, double* loss_hist, int32_t* stop, hipStream_t st, const PrepArgs* pa) {
+  PrepArgs p0;
+  std::memset(&p0, 0, sizeof(p0));
+  const PrepArgs& pp = pa != nullptr && ua.mode == 0 ? *pa : p0;
+  if (!update_prepare_mode_ok(fs, pp.mode)) return hipErrorInvalidValue;
+  if (fs.nf < 1 || fs.nf > TR_MAXF) return hipErrorInvalidValue;
+  GroupArgs g0;
+  std::memset(&g0, 0, sizeof(g0));
+  return update_and_converge<false>(fs, n_bias, params, grad, ua, m, v, vmax, grad_total_out, loss_out, loss_hist,
+                                    stop, st, pp, g0);
 }
 
 hipError_t launch_update_groups(const FactorSet& fs, float* params, const float* grad, const UpdateArgs& ua,
                                 const GroupArgs& ga, float* m, float* v, float* vmax, double* loss_hist,
                                 int32_t* stop, hipStream_t st) {
   if (fs.nf < 1 || fs.nf > TR_MAXF || ua.mode != 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_update_groups, dim3(1), dim3(UPD_T), 0, st, fs, params, grad, ua, ga, m, v, vmax, loss_hist,
-                     stop);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (loss_hist != nullptr && stop != nullptr && ua.iter > ua.patience && ua.tol > 0.0) {
-    hipLaunchKernelGGL(k_converge, dim3(1), dim3(64), 0, st, loss_hist, ua.hist_base, ua.iter, ua.patience,
-                       ua.tol, stop);
-    e = hipGetLastError();
-  }
-  return e;
+  PrepArgs p0;
+  std::memset(&p0, 0, sizeof(p0));
+  return update_and_converge<true>(fs, 0, params, grad, ua, m, v, vmax, nullptr, nullptr, loss_hist, stop, st, p0,
+                                   ga);
 }
 
 }  // namespace tr
@@ -636,6 +532,6 @@ namespace tr {
 // preload_code_objects) instead of at the first launch of one of its kernels
 hipError_t touch_code_object_update() {
   hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_update));
+  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_update<false>));
 }
 }  // namespace tr

@@ -1,5 +1,5 @@
 """GPU checks of the hierarchical multinomial module (multinomial_tensor_regression_hierarchical) and of
-the grouped update step tr_adam_step_groups (k_update_groups).
+the grouped update step tr_adam_step_groups (k_update<true>).
 
   * every hier_* Adam fixture: probabilities, one loss + gradient and the 10-iteration factors at
     1e-5; the full trajectory: losses at 1e-5 with the same length and convergence flag, factors at
@@ -13,7 +13,8 @@ the grouped update step tr_adam_step_groups (k_update_groups).
     launch; a shape sweep (N 1 and 65, P odd and a multiple of 64, C 2 and 16, R 1 and 16, mixed
     non_negative, the largest N that fits) against the fp64 closed form; one sample past the
     envelope takes the streamed route
-  * tr_adam_step_groups on synthetic arenas on both sides of the 1024-thread stride: three distinct
+  * tr_adam_step_groups on synthetic arenas on both sides of the 1024-thread stride and of the
+    2048-element trip (factor boundaries inside a trip, at 2048 + 1 and in the tail): three distinct
     learning rates, one group at lr 0, one factor outside the mask; steps 1 and 1000, with and
     without AMSGrad and weight decay; against fp64 torch.optim.Adam with param groups at the bar of
     tests/test_gpu_update.py (e <= 2 e_torch32 + 2^-22, e the measure of update_ref.err)
@@ -248,6 +249,14 @@ ARENAS = {
     "g3_2180": ((64, 40), 5, 20, 2180),    # three trips
     "g4_126": ((6, 5, 4), 3, 7, 126),
     "g4_1105": ((30, 20, 10), 5, 17, 1105),
+    # 3 * 1024 + 5 elements: the step takes two elements per trip (t, t + 1024), so one full trip
+    # [0, 2048), a second trip for threads 0..4 (2048 + t, 3072 + t) and a one-element tail for the
+    # rest.  The middle factor is the one the "masked" groups leave out.
+    #   boundaries 5 (inside a trip: threads 0..4 hold f0 and f1) and 2049 = 2048 + 1 (thread 0's
+    #   second trip holds 2048 of the masked f1 and 3072 of f2)
+    "g3_3077": ((5, 2044), 1028, 1, 3077),
+    #   boundaries 7 (inside a trip) and 2600 (in the one-element tail)
+    "g3_3077t": ((7, 2593), 477, 1, 3077),
 }
 HP = {
     "plain": ur.hparams(),
@@ -406,7 +415,7 @@ def test_adam_step_groups_against_fp64_param_groups(aname, gname, hpname, t):
     assert ur.err(gt.cpu().numpy(), ref["gtot"]) <= 2.0 * ur.err(yard["gtot"], ref["gtot"]) + FLOOR32
 
 
-@pytest.mark.parametrize("aname", ["g3_1054", "g4_1105"])
+@pytest.mark.parametrize("aname", ["g3_1054", "g4_1105", "g3_3077", "g3_3077t"])
 def test_adam_step_groups_one_lr_is_bitwise_adam_step(aname):
     a = arena_of(aname)
     if a.nf != 3:

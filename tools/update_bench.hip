@@ -1,4 +1,4 @@
-// update_bench.hip — layout study for the one-workgroup Adam step (k_update, tr_kernels.hip).
+// update_bench.hip — layout study for the one-workgroup Adam step (k_update, tr_update.hip).
 //
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I tensor_regression_amd/csrc tools/update_bench.hip -o tools/_update_bench
 //   rocprofv3 --kernel-trace --stats -d gpurun_out/ub -o ub -- tools/_update_bench
