@@ -35,6 +35,7 @@
 #include <cstring>
 
 #include "tr_conv_spectrum.h"
+#include "tr_workspace.h"
 
 namespace tr {
 
@@ -232,8 +233,6 @@ void dft_split(int64_t A, int64_t B, int N, int* nsplit, int64_t* bper) {
   *nsplit = (int)((tiles + tper - 1) / tper);
 }
 
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <int ADJ>
 hipError_t launch_dft(const SpecPen& sp, const SpecBufs& b, int64_t A, int64_t B, const float* in0, const float* in1,
                       float* out0, float* out1, float* mag, const int32_t* stop, hipStream_t st) {
@@ -256,30 +255,24 @@ size_t spec_carve(const SpecPen& sp, int64_t max_rows, char* base, SpecBufs* b) 
   const size_t FN = (size_t)sp.F * sp.N, FsN = (size_t)sp.Fs * sp.N, RN = (size_t)max_rows * sp.N;
   const size_t amax = FN > RN ? FN : RN;
   // splits * outputs <= 2^20 + A N (dft_split: splits <= 1024 / workgroups + 1, workgroups >= A N / 1024)
-  const size_t b_part = al256(2 * (((size_t)1 << 20) + amax) * 8);
-  const size_t b_pp = al256(((FsN + PEN_EPB - 1) / PEN_EPB) * 8);
-  const size_t sz[] = {al256((size_t)sp.nfft * 8), al256((size_t)sp.S * 4), al256(FN * 4), al256(FN * 4),
-                       al256(FN * 4), al256(FsN * 4), al256(FsN * 4), al256(FsN * 4), b_part, b_pp, 256,
-                       al256(RN * 4), al256(RN * 4)};
-  size_t off[14];
-  off[0] = 0;
-  for (int i = 0; i < 13; ++i) off[i + 1] = off[i] + sz[i];
-  if (base != nullptr && b != nullptr) {
-    b->tw = (float2*)(base + off[0]);
-    b->g = (float*)(base + off[1]);
-    b->re = (float*)(base + off[2]);
-    b->im = (float*)(base + off[3]);
-    b->A = (float*)(base + off[4]);
-    b->M = (float*)(base + off[5]);
-    b->My = (float*)(base + off[6]);
-    b->dM = (float*)(base + off[7]);
-    b->part = (double*)(base + off[8]);
-    b->ppart = (double*)(base + off[9]);
-    b->val = (float*)(base + off[10]);
-    b->yhat = (float*)(base + off[11]);
-    b->eadd = (float*)(base + off[12]);
-  }
-  return off[13];
+  SpecBufs sized;  // (size only: the slots of a call without a base)
+  if (base == nullptr || b == nullptr) b = &sized;
+  Carver c;
+  c.add(&b->tw, (size_t)sp.nfft * 8);
+  c.add(&b->g, (size_t)sp.S * 4);
+  c.add(&b->re, FN * 4);
+  c.add(&b->im, FN * 4);
+  c.add(&b->A, FN * 4);
+  c.add(&b->M, FsN * 4);
+  c.add(&b->My, FsN * 4);
+  c.add(&b->dM, FsN * 4);
+  c.add(&b->part, 2 * (((size_t)1 << 20) + amax) * 8);
+  c.add(&b->ppart, ((FsN + PEN_EPB - 1) / PEN_EPB) * 8);
+  c.add(&b->val, 4);
+  c.add(&b->yhat, RN * 4);
+  c.add(&b->eadd, RN * 4);
+  if (b != &sized) c.bind(base);
+  return c.bytes();
 }
 
 void spec_build_twiddles(int64_t nfft, float2* tw) {

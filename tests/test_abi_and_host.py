@@ -52,6 +52,35 @@ def test_argument_validation_without_gpu():
         assert rc > 0 and lib.tr_last_error()
 
 
+def test_every_creator_reports_a_missing_device():
+    """Without a device a well-formed call to each plan creator fails at opening it: rc > 0 (a HIP error),
+    *out left NULL and tr_last_error() set.  Walks every constructor's early exit, where the plan built
+    so far is released by its owner.  (Not run where a GPU is present: no bad device index is passed.)"""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a HIP device is present: the creators succeed (tests/test_gpu_plan_lifecycle.py)")
+    from tensor_regression_amd import _lib
+    lib = _lib.load()
+    dims = (ctypes.c_int64 * 2)(4, 3)
+    nn = (ctypes.c_int32 * 3)(0, 0, 0)
+    conv = (7, 4, 2, 1, 1)  # n_w, n_d, n_out, rank_normal, rank_spectral
+    creators = {
+        "linear": lambda h: lib.tr_plan_create(h, 0, _lib.TR_MODEL_LINEAR, 2, dims, 1, 2, 8, nn, 50.0, 1.0),
+        "multinomial": lambda h: lib.tr_plan_create(h, 0, _lib.TR_MODEL_MULTINOMIAL, 2, dims, 3, 2, 8, nn, 50.0, 1.0),
+        "spectral": lambda h: lib.tr_plan_create_spectral(h, 0, 8, 5, 1, 2, 2, 2, 4, nn, 50.0, 1.0),
+        "conv": lambda h: lib.tr_plan_create_conv(h, 0, *conv, 2, 600, nn, 50.0, 1.0),
+        "conv_phase": lambda h: lib.tr_plan_create_conv_phase(h, 0, *conv, 600, nn, 50.0, 1.0),
+        "conv_fourier": lambda h: lib.tr_plan_create_conv_fourier(h, 0, *conv, 2, 600, nn, 50.0, 1.0),
+        "f64": lambda h: lib.tr_plan_create_f64(h, 0, 2, dims, 2, 8, nn, 50.0, 1.0),
+    }
+    for name, create in creators.items():
+        h = ctypes.c_void_p(0xdead)  # the creator must reset it
+        rc = create(ctypes.byref(h))
+        assert rc > 0, (name, rc)
+        assert not h.value, name
+        assert lib.tr_last_error(), name
+
+
 def test_no_cpu_fallback_in_product():
     """The product package never imports the oracle."""
     pkg = os.path.join(ROOT, "tensor_regression_amd")
