@@ -291,6 +291,57 @@ int tr_fit_adam_resident(tr_plan* plan, const float* X, int64_t n_rows, const vo
                          void* stream);
 
 /*
+ * Resident sweep: many independent resident fits in one launch, workgroup j fitting member j
+ * (a hyperparameter grid: one model per grid point, each with its own data, shape, initial
+ * factors and optimizer settings).  No plan is involved.  A member carries the arguments of
+ * tr_fit_adam_resident and what that call takes from its plan: the shape (I0, I1, n_classes, rank;
+ * inside the envelope above, which is checked per member at its own n_rows), nonneg[3], the
+ * softplus beta / threshold and X's row stride in floats (0 = I0 * I1).  Members may differ in
+ * every field.  n_iters is 0..64: a member with n_iters = 0 (finished, or shorter than the
+ * others) is left untouched, as is one whose *stop_flag is nonzero.  Member j's results are
+ * bitwise those of tr_fit_adam_resident on the same inputs.
+ *   tr_resident_member_table_bytes  size of the launch's argument table for n_members
+ *   tr_fit_adam_resident_many       checks EVERY member before any device call (NULL buffer,
+ *                                   n_rows < 1, n_iters outside 0..64, step < 1, iter or
+ *                                   hist_base < 0, lr < 0, amsgrad without max_exp_avg_sq:
+ *                                   TR_E_ARG; outside the envelope: TR_E_UNSUPPORTED;
+ *                                   tr_last_error() names the member's index) and launches
+ *                                   nothing if one fails.  table_host (pinned host memory) and
+ *                                   table_dev (memory of `device`), each of at least table_bytes >=
+ *                                   tr_resident_member_table_bytes(n_members), are the caller's: the
+ *                                   table is written to table_host and copied to table_dev on
+ *                                   `stream` ahead of the launch, so table_host must not be
+ *                                   reused before that copy has completed.
+ */
+typedef struct tr_resident_member {
+  const float* X;        /* (n_rows, I0, I1) at x_row_stride */
+  const void* target;    /* int64 labels [n_rows] */
+  float* params;         /* (I0 + I1 + n_classes) * rank: the three factors, contiguous */
+  const float* weights;  /* [rank] CP component weights */
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* max_exp_avg_sq; /* amsgrad only, else may be NULL */
+  double* loss_hist;
+  int32_t* stop_flag;
+  int64_t n_rows, x_row_stride;
+  int64_t I0, I1;
+  int32_t n_classes, rank;
+  int32_t nonneg[3];
+  int32_t amsgrad;
+  float softplus_beta, softplus_threshold;
+  float lambda_l2;
+  int32_t n_iters;
+  double lr[3];
+  double beta1, beta2, eps, weight_decay;
+  int64_t step, hist_base, iter, patience;
+  double tol;
+} tr_resident_member;
+
+int64_t tr_resident_member_table_bytes(int n_members);
+int tr_fit_adam_resident_many(int device, const tr_resident_member* members, int n_members, void* table_host,
+                              void* table_dev, int64_t table_bytes, void* stream);
+
+/*
  * Fold the NEXT iteration's factor preparation into tr_adam_step: with enable = 1, on a plan
  * that takes the factored multinomial single pass, every tr_adam_step also computes
  * softplus(A_k) and its derivative from the parameters it has just written, and the following

@@ -12,6 +12,7 @@ import ctypes
 import math
 import os
 import sys
+import time
 import types
 import weakref
 
@@ -1230,6 +1231,114 @@ def run_adam_fit_groups(plan, X, target, class_weight, norm, arena, weights, lam
 
     return _adam_loop(plan, torch.float32, hp, loss_running, max_iter, tol, verbose_cb, sync_every,
                       one_launch if resident else streamed)
+
+
+def resident_max_rows(I0, I1, n_classes, rank):
+    """tr_mnl_resident_max_rows: the largest sample count the resident fit holds for this shape (0: none)."""
+    return int(_lib.load().tr_mnl_resident_max_rows(int(I0), int(I1), int(n_classes), int(rank)))
+
+
+def resident_enabled():
+    """The test-facing switch tr_plan_set_resident reads: TR_MNL_RESIDENT=0 keeps the streamed route."""
+    return not os.environ.get("TR_MNL_RESIDENT", "").startswith("0")
+
+
+def run_resident_many(dev, members, sync_every=64, trace=None):
+    """Fit many independent models on the resident route together (tr_fit_adam_resident_many): every
+    chunk of up to `sync_every` (<= 64) iterations is ONE launch whose workgroup j runs member j.
+
+    `members`: objects with X (N, I0, I1) float32 and y int64 on cuda:`dev`, arena (the three factors,
+    packed), w [R], n_classes, rank, nonneg[3], beta, thr (softplus), lambda_L2, hp (adam_hparams),
+    lr_at(ii) -> three learning rates, breaks (loop indices where a learning rate changes), max_iter,
+    tol, patience and loss_running (extended in place, as run_adam_fit_groups does).  All members start
+    at loop index 0 and advance together; a chunk is cut at the union of the members' breaks (lr is
+    constant per launch, and cutting never changes the bits); a member past its own max_iter or
+    stopped on its plateau gets n_iters = 0 from then on.  One host sync per chunk: the copy of the
+    int32[M] stop array.  Returns (stop values, launches): stop > 0 is a plateau after that many
+    iterations.  `trace` (a list, for tools/hier_many_shapes.py) receives per launch (iterations,
+    ms between device events around the table upload and the kernel, ms of wall time of the chunk)."""
+    lib = _lib.load()
+    M = len(members)
+    device = f"cuda:{dev}"
+    seg = lambda n: -(-n // 64) * 64  # 256-byte aligned segments
+    # one zeroed buffer for every member's Adam state, one for the loss histories, one stop array
+    state_at, hist_at, ns, nh = [], [], 0, 0
+    for mb in members:
+        P = mb.arena.numel()
+        state_at.append(ns)
+        ns += 3 * seg(P)
+        hist_at.append(nh)
+        nh += seg(len(mb.loss_running) + max(int(mb.max_iter), 0) + 1)
+    hist_host = np.zeros(nh, dtype=np.float64)
+    for mb, at in zip(members, hist_at):  # the plateau test reads the earlier losses
+        if mb.loss_running:
+            hist_host[at:at + len(mb.loss_running)] = mb.loss_running
+    with torch.cuda.device(dev):
+        state = torch.zeros(ns, dtype=torch.float32, device=device)
+        hist = torch.from_numpy(hist_host).to(device)
+        stop = torch.zeros(M, dtype=torch.int32, device=device)
+        nbytes = int(lib.tr_resident_member_table_bytes(M))
+        table_host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        table_dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    arr = (_lib.ResidentMember * M)()
+    rec = np.frombuffer(arr, dtype=np.dtype(_lib.ResidentMember))  # the same memory, column-wise
+    for j, mb in enumerate(members):
+        r, P = arr[j], mb.arena.numel()
+        N, I0, I1 = (int(d) for d in mb.X.shape)
+        s0 = state_at[j]
+        r.X, r.target, r.params, r.weights = mb.X.data_ptr(), mb.y.data_ptr(), mb.arena.data_ptr(), mb.w.data_ptr()
+        r.exp_avg = state[s0:].data_ptr()
+        r.exp_avg_sq = state[s0 + seg(P):].data_ptr()
+        r.max_exp_avg_sq = state[s0 + 2 * seg(P):].data_ptr() if mb.hp["amsgrad"] else None
+        r.loss_hist = hist[hist_at[j]:].data_ptr()
+        r.stop_flag = stop[j:].data_ptr()
+        r.n_rows, r.I0, r.I1, r.n_classes, r.rank = N, I0, I1, int(mb.n_classes), int(mb.rank)
+        r.x_row_stride = int(mb.X.stride(0)) if N > 1 else I0 * I1
+        for f in range(3):
+            r.nonneg[f] = 1 if mb.nonneg[f] else 0
+        r.amsgrad = 1 if mb.hp["amsgrad"] else 0
+        r.softplus_beta, r.softplus_threshold, r.lambda_l2 = float(mb.beta), float(mb.thr), float(mb.lambda_L2)
+        r.beta1, r.beta2, r.eps, r.weight_decay = (mb.hp[k] for k in ("beta1", "beta2", "eps", "weight_decay"))
+        r.hist_base, r.patience, r.tol = len(mb.loss_running), int(mb.patience), float(mb.tol)
+    max_iters = np.array([max(int(mb.max_iter), 0) for mb in members], dtype=np.int64)
+    breaks = sorted({int(b) for mb in members for b in mb.breaks})
+    lrs_const = all(not mb.breaks for mb in members)
+    stops = np.zeros(M, dtype=np.int32)
+    ii, launches, first = 0, 0, True
+    stream = stream_handle(dev)
+    t_chunk = time.perf_counter()
+    while True:
+        left = np.where(stops == 0, max_iters - ii, 0)
+        if not (left > 0).any():
+            break
+        n = min([int(sync_every), int(left.max())] + [b - ii for b in breaks if b > ii])
+        rec["n_iters"] = np.clip(left, 0, n)
+        rec["step"] = ii + 1
+        rec["iter"] = ii
+        if first or not lrs_const:
+            rec["lr"] = np.array([mb.lr_at(ii)[:3] for mb in members], dtype=np.float64).reshape(M, 3)
+        first = False
+        with torch.cuda.device(dev):
+            if trace is not None:
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev[0].record()
+            check(lib.tr_fit_adam_resident_many(dev, arr, M, ptr(table_host), ptr(table_dev), nbytes, stream),
+                  "tr_fit_adam_resident_many")
+            launches += 1
+            if trace is not None:
+                ev[1].record()
+            stops = stop.cpu().numpy()  # the one host sync of the chunk (table_host is free again after it)
+            if trace is not None:
+                now = time.perf_counter()
+                trace.append((n, ev[0].elapsed_time(ev[1]), (now - t_chunk) * 1e3))
+                t_chunk = now
+        ii += n
+    hist_host = hist.cpu().numpy()
+    for j, mb in enumerate(members):
+        n_run = abs(int(stops[j])) if stops[j] else int(max_iters[j])
+        base = hist_at[j] + len(mb.loss_running)
+        mb.loss_running.extend(hist_host[base:base + n_run].tolist())
+    return [int(s) for s in stops], launches
 
 
 def _adam_loop(plan, fdt, hp, loss_running, max_iter, tol, verbose_cb, sync_every, chunk, wait=None):

@@ -24,9 +24,24 @@ TR_MODEL_CONV_FOURIER = 5
 TR_MAX_FACTORS = 8
 KERNEL_KINDS = ["stream_fused", "stream_rows", "stream_cols", "reduce", "mttkrp", "prep", "update"]
 
-# exported symbol -> (restype, argtypes)
 _c = ctypes
 _vp = _c.c_void_p
+
+
+class ResidentMember(_c.Structure):
+    """`tr_resident_member`: one member of tr_fit_adam_resident_many (fields in the header's order)."""
+    _fields_ = [("X", _vp), ("target", _vp), ("params", _vp), ("weights", _vp), ("exp_avg", _vp),
+                ("exp_avg_sq", _vp), ("max_exp_avg_sq", _vp), ("loss_hist", _vp), ("stop_flag", _vp),
+                ("n_rows", _c.c_int64), ("x_row_stride", _c.c_int64), ("I0", _c.c_int64), ("I1", _c.c_int64),
+                ("n_classes", _c.c_int32), ("rank", _c.c_int32), ("nonneg", _c.c_int32 * 3),
+                ("amsgrad", _c.c_int32), ("softplus_beta", _c.c_float), ("softplus_threshold", _c.c_float),
+                ("lambda_l2", _c.c_float), ("n_iters", _c.c_int32), ("lr", _c.c_double * 3),
+                ("beta1", _c.c_double), ("beta2", _c.c_double), ("eps", _c.c_double),
+                ("weight_decay", _c.c_double), ("step", _c.c_int64), ("hist_base", _c.c_int64),
+                ("iter", _c.c_int64), ("patience", _c.c_int64), ("tol", _c.c_double)]
+
+
+# exported symbol -> (restype, argtypes)
 SIGNATURES = {
     "tr_abi_version": (_c.c_int, []),
     "tr_last_error": (_c.c_char_p, []),
@@ -82,6 +97,9 @@ SIGNATURES = {
                                         _c.POINTER(_c.c_double), _c.c_double, _c.c_double, _c.c_double, _c.c_double,
                                         _c.c_int, _c.c_int64, _c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int64,
                                         _c.c_double, _vp, _vp]),
+    "tr_resident_member_table_bytes": (_c.c_int64, [_c.c_int]),
+    "tr_fit_adam_resident_many": (_c.c_int, [_c.c_int, _c.POINTER(ResidentMember), _c.c_int, _vp, _vp, _c.c_int64,
+                                             _vp]),
     "tr_plan_set_prepare_next": (_c.c_int, [_vp, _c.c_int]),
     "tr_plan_create_f64": (_c.c_int, [_c.POINTER(_vp), _c.c_int, _c.c_int, _c.POINTER(_c.c_int64), _c.c_int,
                                       _c.c_int64, _c.POINTER(_c.c_int32), _c.c_double, _c.c_double]),

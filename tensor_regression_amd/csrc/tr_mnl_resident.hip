@@ -27,6 +27,11 @@
 // fit cut into launches of any lengths, give the same bits.  lr is constant within a launch (the
 // host cuts the chunk at a group_lr breakpoint).
 //
+// Two entry points run that one body (resident_fit): k_mnl_resident, one workgroup whose arguments are
+// the kernel's own, and k_mnl_resident_many, a grid in which workgroup j fits member j of a table in
+// global memory (a hyperparameter sweep: independent models, each with its own shape, data and
+// optimizer settings).  The workgroups share nothing, so member j's bits are the single launch's.
+//
 // LDS image (ResGeom): X at an odd row pitch, so the Z pass (lanes over samples, stride XP) and the G
 // pass (lanes over features, stride 1) both touch 32 distinct banks per half wave; Z at an odd pitch
 // for the same reason; B and dZ are read at wave-uniform addresses (broadcast).
@@ -38,40 +43,14 @@
 
 namespace tr {
 
-bool resident_geom(int64_t N, int64_t I0, int64_t I1, int C, int R, ResGeom* g) {
-  if (N < 1 || I0 < 1 || I1 < 1 || C < 1 || C > RES_MAX_C || R < 1 || R > RES_MAX_R) return false;
-  const int64_t P = I0 * I1;
-  if (N > 65536 || P > 65536) return false;  // far past what 160 KiB holds; keeps the words in int
-  const int64_t XP = P | 1, CP = C | 1, PC = P * C;
-  int64_t S = RES_T / PC;
-  if (S > 8) S = 8;
-  if (S > N) S = N;
-  if (S < 1) S = 1;
-  const int64_t np = (I0 + I1 + C) * R;
-  int64_t o = 32 + 8;  // 16 fp64 loss partials, then the control words
-  auto take = [&](int64_t n) {
-    const int64_t at = o;
-    o += (n + 3) & ~(int64_t)3;
-    return at;
-  };
-  const int64_t oX = take(N * XP), oB = take(PC), oG = take(PC), oGp = take(S > 1 ? S * PC : 0), oZ = take(N * CP),
-                oY = take(N), oW = take(R), oPar = take(np), oM = take(np), oV = take(np), oVm = take(np),
-                oPhi = take(np), oDphi = take(np), oGrad = take(np), oNorm = take(8);
-  if (o * 4 > RES_LDS_BYTES) return false;
-  if (g != nullptr) {
-    *g = ResGeom{(int)N, (int)I0, (int)I1, (int)P, C, R, (int)XP, (int)CP, (int)S, (int)np, (int)(I0 * R),
-                 (int)((I0 + I1) * R), (int)oX, (int)oB, (int)oG, (int)oGp, (int)oZ, (int)oY, (int)oW, (int)oPar,
-                 (int)oM, (int)oV, (int)oVm, (int)oPhi, (int)oDphi, (int)oGrad, (int)oNorm, (int)o};
-  }
-  return true;
-}
-
-__global__ __launch_bounds__(RES_T) void k_mnl_resident(ResArgs a, const float* __restrict__ X, int64_t xld,
-                                                        const int64_t* __restrict__ target,
-                                                        float* __restrict__ params, const float* __restrict__ w,
-                                                        float* __restrict__ m, float* __restrict__ v,
-                                                        float* __restrict__ vmax, double* __restrict__ loss_hist,
-                                                        int32_t* __restrict__ stop) {
+// The fit of one problem by the calling workgroup: load, phases 1-8 per iteration, write-back.  `a` is
+// read through a wave-uniform address (the kernel arguments, or this workgroup's row of the member
+// table in global memory), so its fields arrive by scalar loads; it is not copied into the LDS image.
+static __device__ __forceinline__ void resident_fit(const ResArgs& a, const float* __restrict__ X, int64_t xld,
+                                                    const int64_t* __restrict__ target, float* __restrict__ params,
+                                                    const float* __restrict__ w, float* __restrict__ m,
+                                                    float* __restrict__ v, float* __restrict__ vmax,
+                                                    double* __restrict__ loss_hist, int32_t* __restrict__ stop) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const ResGeom& g = a.g;
@@ -306,8 +285,32 @@ __global__ __launch_bounds__(RES_T) void k_mnl_resident(ResArgs a, const float* 
   if (t == 0 && ctrl[0] != 0) *stop = ctrl[0];
 }
 
+__global__ __launch_bounds__(RES_T) void k_mnl_resident(ResArgs a, const float* __restrict__ X, int64_t xld,
+                                                        const int64_t* __restrict__ target,
+                                                        float* __restrict__ params, const float* __restrict__ w,
+                                                        float* __restrict__ m, float* __restrict__ v,
+                                                        float* __restrict__ vmax, double* __restrict__ loss_hist,
+                                                        int32_t* __restrict__ stop) {
+  resident_fit(a, X, xld, target, params, w, m, v, vmax, loss_hist, stop);
+}
+
+// Workgroup j fits member j of the table; the workgroups share nothing (no atomics, no waiting on one
+// another), so the grid may exceed the CUs and run in waves.  A member with n_iters == 0 (finished, or
+// fewer iterations than the others) and one whose stop word is set leave before any barrier; both
+// tests are uniform over the workgroup.  The launch's dynamic LDS is the largest member's carve.
+__global__ __launch_bounds__(RES_T) void k_mnl_resident_many(const ResMember* __restrict__ members, int n_members) {
+  const int j = blockIdx.x;
+  if (j >= n_members) return;
+  const ResMember& mb = members[j];
+  if (mb.a.n_iters <= 0) return;
+  resident_fit(mb.a, mb.X, mb.xld, mb.target, mb.params, mb.w, mb.m, mb.v, mb.vmax, mb.loss_hist, mb.stop);
+}
+
 hipError_t prepare_resident() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mnl_resident),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mnl_resident),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)RES_LDS_BYTES);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mnl_resident_many),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)RES_LDS_BYTES);
 }
 
@@ -318,6 +321,12 @@ hipError_t launch_resident(const ResArgs& a, const float* X, int64_t xld, const 
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_mnl_resident, dim3(1), dim3(RES_T), (size_t)a.g.words * 4, st, a, X, xld, target, params, w, m,
                      v, vmax, loss_hist, stop);
+  return hipGetLastError();
+}
+
+hipError_t launch_resident_many(const ResMember* members, int n_members, int64_t lds_bytes, hipStream_t st) {
+  if (members == nullptr || n_members < 1 || lds_bytes < 1 || lds_bytes > RES_LDS_BYTES) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_mnl_resident_many, dim3(n_members), dim3(RES_T), (size_t)lds_bytes, st, members, n_members);
   return hipGetLastError();
 }
 

@@ -20,19 +20,22 @@ The fit runs the multinomial plan (class weights of ones, normaliser N) with the
 `fit_Adam(weights=np.ones(C))`.
 """
 import bisect
+import functools
 import math
 import numbers
+import types
 
 import numpy as np
 import torch
 
+from . import _engine
 from ._engine import adam_hparams, run_adam_fit_groups
 from . import multinomial_tensor_regression as _mnl
 from .multinomial_tensor_regression import (squeeze_integers, confusion_matrix, idx_to_oneHot,  # noqa: F401
                                             make_BcpInit, non_neg_fn, model, L2_penalty, _Verbose)
 
 __all__ = ["squeeze_integers", "confusion_matrix", "idx_to_oneHot", "make_BcpInit", "non_neg_fn", "model",
-           "L2_penalty", "CP_logistic_regression"]
+           "L2_penalty", "CP_logistic_regression", "fit_Adam_many"]
 
 N_GROUPS = 3  # hierarchical…py:436-440: Bcp[0], Bcp[1], Bcp[2]
 
@@ -90,6 +93,138 @@ def lr_in_force(schedule, ii):
     """The three learning rates at loop index ii: for each group the lr of the last pair with
     first_iteration <= ii (`optimizer.param_groups[g]['lr'] = lr` run at the top of that iteration)."""
     return [lrs[bisect.bisect_right(starts, ii) - 1] for starts, lrs in schedule]
+
+
+def _seq(x):
+    return hasattr(x, "__len__") and not isinstance(x, (str, bytes, dict))
+
+
+def _one_schedule(value):
+    """Whether `value` reads as ONE group_lr (three entries, each a number or a list of (first_iteration,
+    lr) pairs) rather than a list of one group_lr per model (entries None or themselves three-entry
+    sequences, whose elements are numbers or lists of pairs — never pairs)."""
+    return _seq(value) and len(value) == N_GROUPS and all(
+        _is_number(e) or (_seq(e) and len(e) > 0 and all(_seq(x) and len(x) > 0 and _is_number(x[0]) for x in e))
+        for e in value)
+
+
+def _per_member(name, value, M):
+    """One value for all M models, or a list of M values (ValueError on another length)."""
+    if name == "group_lr":
+        per = isinstance(value, list) and not _one_schedule(value)
+    else:
+        per = isinstance(value, (list, tuple))
+    if not per:
+        return [value] * M
+    if len(value) != M:
+        raise ValueError(f"{name}: a list must hold one value per model ({M}), got {len(value)}")
+    return list(value)
+
+
+def fit_Adam_many(models, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, verbose=False, Adam_kwargs=None,
+                  group_lr=None, report=None):
+    """fit_Adam of many independent models at once — the outer loop of a hyperparameter grid
+    (demo_tensorRegression_forKim.ipynb: one freshly built model per grid point) as one launch per 64
+    iterations, one workgroup per model.
+
+    models: CP_logistic_regression objects of this module, each with its own X, y, rank, non_negative
+    and initial factors.  lambda_L2, max_iter, tol, patience, Adam_kwargs and group_lr are each one
+    value for all models or a list of len(models) values.  Afterwards every model is in exactly the
+    state its own `model.fit_Adam(...)` with its own arguments would have left it (Bcp bitwise,
+    loss_running extended); the returned list holds each model's convergence_reached.
+
+    A model inside the resident envelope (3-D X, n_classes and rank <= 16, the problem within one
+    CU's LDS; TR_MNL_RESIDENT not 0) is fitted in the batch; every other model by its own fit_Adam,
+    one after another.  report (a dict) receives {'batched': indices, 'alone': indices, 'launches': n}.
+    verbose=2 (a line per iteration) is not offered: it would force one launch per iteration."""
+    models = list(models)
+    M = len(models)
+    if verbose == 2:
+        raise NotImplementedError("fit_Adam_many: verbose=2 prints every iteration, which forces one launch per "
+                                  "iteration per model; call fit_Adam on each model instead")
+    given = dict(lambda_L2=lambda_L2, max_iter=max_iter, tol=tol, patience=patience, Adam_kwargs=Adam_kwargs,
+                 group_lr=group_lr)
+    args = {k: _per_member(k, v, M) for k, v in given.items()}
+    if len({id(m) for m in models}) != M:
+        raise ValueError("fit_Adam_many: the same model object appears twice")
+    for m in models:
+        if not isinstance(m, CP_logistic_regression):
+            raise TypeError(f"fit_Adam_many takes this module's CP_logistic_regression objects, got {type(m).__name__}")
+    if report is not None:
+        report.clear()
+        report.update(batched=[], alone=[], launches=0)
+    if M == 0:
+        return []
+    # every member's own argument errors, in fit_Adam's order, before anything is launched
+    hps, schedules = [], []
+    for j, m in enumerate(models):
+        ak = args["Adam_kwargs"][j]
+        if ak is None:
+            raise TypeError("'NoneType' object is not subscriptable")
+        m.Bcp[0]
+        lr0 = ak['lr']  # KeyError without 'lr'
+        m.Bcp[1]
+        m.Bcp[2]  # IndexError on a 2-D X
+        hps.append(adam_hparams(ak))
+        schedules.append(resolve_group_lr(args["group_lr"][j], lr0))
+        _check_lr(lr0, " (Adam_kwargs['lr'])")
+    devs = {_engine.compute_device(m.X, m.device) for m in models}
+    if len(devs) != 1:
+        raise ValueError(f"fit_Adam_many: the models are on different devices ({sorted(devs)})")
+    dev = devs.pop()
+    on = _engine.resident_enabled()
+    batched, alone = [], []
+    for j, m in enumerate(models):
+        inside = (on and len(m.Bcp) == N_GROUPS and getattr(m.X, "ndim", 0) == 3 and int(m.X.shape[0]) <= _engine.resident_max_rows(
+            m.Bcp[0].shape[0], m.Bcp[1].shape[0], m.Bcp[2].shape[0], m.Bcp[0].shape[1]))
+        (batched if inside else alone).append(j)
+    results = [False] * M
+    launches = 0
+    if batched:
+        members, srcs, offsets, total = [], [], [], 0
+        for j in batched:
+            m = models[j]
+            _, Xd, yd = m._device_data()
+            dims = [int(A.shape[0]) for A in m.Bcp]
+            if list(Xd.shape[1:]) != dims[:2]:
+                raise ValueError(f"Incorrect shapes for inner product along 2 common modes. "
+                                 f"tensor_1.shape={list(Xd.shape)}, factors={[tuple(A.shape) for A in m.Bcp]}")
+            R = int(m.Bcp[0].shape[1])
+            nn, beta, thr = _engine.nonlin_key(m.non_negative, m.softplus_kwargs, N_GROUPS)
+            mb = types.SimpleNamespace(
+                X=Xd, y=yd, n_classes=dims[2], rank=R, nonneg=nn, beta=beta, thr=thr, lambda_L2=args["lambda_L2"][j],
+                hp=hps[j], lr_at=functools.partial(lr_in_force, schedules[j]),
+                breaks=sorted({s for starts, _ in schedules[j] for s in starts[1:]}), max_iter=args["max_iter"][j],
+                tol=args["tol"][j], patience=args["patience"][j], loss_running=m.loss_running,
+                w=m.weights.to(f"cuda:{dev}", torch.float32).contiguous())
+            for f, A in enumerate(m.Bcp):
+                A = torch.as_tensor(A)
+                if tuple(A.shape) != (dims[f], R):
+                    raise ValueError(f"factor {f} has shape {tuple(A.shape)}, expected {(dims[f], R)}")
+                srcs.append(A.detach().reshape(-1))
+                offsets.append(total)
+                total += dims[f] * R
+            members.append(mb)
+        # every member's factors in ONE arena (one launch to pack, one to write back), a slice each
+        arena = _engine._pack_arena(srcs, total, torch.float32, f"cuda:{dev}")
+        bounds = offsets + [total]
+        for k, mb in enumerate(members):
+            mb.arena = arena[bounds[3 * k]:bounds[3 * k + 3]]
+        stops, launches = _engine.run_resident_many(dev, members)
+        _engine._unpack_arena(arena, offsets, [A for j in batched for A in models[j].Bcp])
+        for j, s in zip(batched, stops):
+            results[j] = s > 0
+    for j in alone:  # outside the envelope (or the route switched off): the model's own fit, one after another
+        results[j] = models[j].fit_Adam(lambda_L2=args["lambda_L2"][j], max_iter=args["max_iter"][j],
+                                        tol=args["tol"][j], patience=args["patience"][j], verbose=False,
+                                        Adam_kwargs=args["Adam_kwargs"][j], group_lr=args["group_lr"][j])
+    if (verbose is True) or (verbose >= 1):
+        for j, conv in enumerate(results):
+            print(f"model {j}: " + ('Convergence reached' if conv else
+                                    'Reached maximum number of iterations without convergence'))
+    if report is not None:
+        report.update(batched=batched, alone=alone, launches=launches)
+    return results
 
 
 class CP_logistic_regression(_mnl.CP_logistic_regression):
