@@ -107,7 +107,8 @@ int64_t tr_plan_num_params(const tr_plan* plan); /* factors (+ bias) */
 int64_t tr_plan_num_grads(const tr_plan* plan);  /* num_params + 2 (data-loss + status slots) */
 int64_t tr_plan_factor_offset(const tr_plan* plan, int factor);
 int64_t tr_plan_workspace_bytes(const tr_plan* plan);
-/* Human-readable description of the kernel strategy chosen for this plan (host string). */
+/* Human-readable description of the kernel strategy the next call on this plan runs (host string):
+ * written at creation and rewritten whenever tr_plan_set_x_stride re-chooses the strategy. */
 const char* tr_plan_describe(const tr_plan* plan);
 
 /*
@@ -117,7 +118,8 @@ const char* tr_plan_describe(const tr_plan* plan);
  * (util.py:67-114, WindowedDataset: sample n = rows [n + w0, n + w1) of an untiled (T, F...)
  * series) without materialising them: stride = F, P = window * F.  The vector (16-byte) kernel
  * paths need stride % 4 == 0 and a 16-byte aligned X; otherwise the plan switches to its scalar
- * paths, and a misaligned X on a vector plan is rejected with TR_E_ARG.
+ * paths, and a misaligned X on a vector plan is rejected with TR_E_ARG.  tr_plan_describe follows
+ * the re-chosen strategy; stride 0 restores the creation-time strategy and its text.
  */
 int tr_plan_set_x_stride(tr_plan* plan, int64_t stride);
 

@@ -349,7 +349,7 @@ LIN_SHAPES = [
     ((300, 256, 128), 8),      # config-2 row width (fused T=1024 CH=8)
     ((257, 6, 7, 8, 3), 5),    # 4 feature modes, unaligned
     ((64, 10, 10), 33),        # rank > 32 (RMAX 64 MTTKRP)
-    ((129, 100, 101), 2),      # P % 4 != 0: the fused pass over 4-B aligned rows, the last quad partial
+    ((129, 100, 101), 2),      # P = 10100 (a multiple of 4): the fused pass over a row padded to T = 512, CH = 5
     ((300, 64, 64, 32), 16),   # config-4 row (P = 131072 > LDS): cluster single pass, 5 slices
     ((77, 45000), 3),          # one wide mode: 2-slice cluster, ragged last slice
     ((2, 200, 332), 4),        # N < number of clusters: most clusters own no rows
@@ -370,9 +370,18 @@ LIN_SHAPES = [
     ((777, 12, 10), 5),        # P = 120: PQ = 32, 2 rows per wave
     ((999, 5, 5, 5), 3),       # P = 125
     ((3, 4, 4), 2),            # fewer rows than one block
+    # (appended: the ids of the cases above carry their index)
+    # P % 4 != 0 above one wave of columns: the fused pass over 4-B aligned rows with a partial last quad at
+    # CH = 1 and CH > 1 (the slab stride into k_reduce_slabs is 4 ceil(P / 4)); under twopass, k_rows /
+    # k_cols at W = 1
+    ((150, 11, 13), 3),        # P = 143
+    ((120, 33, 31), 3),        # P = 1023
+    ((90, 101, 99), 3),        # P = 9999
+    ((60, 127, 129), 3),       # P = 16383
 ]
 PADDED_FUSED = [((200, 100, 100), 4), ((150, 160, 160), 8), ((90, 250, 130), 3), ((129, 100, 101), 2),
-                ((7, 5, 3), 1), ((257, 6, 7, 8, 3), 5)]
+                ((7, 5, 3), 1), ((257, 6, 7, 8, 3), 5),
+                ((150, 11, 13), 3), ((120, 33, 31), 3), ((90, 101, 99), 3), ((60, 127, 129), 3)]
 
 
 @pytest.mark.parametrize("shape,rank", PADDED_FUSED)
