@@ -344,6 +344,63 @@ int tr_fit_adam_resident_many(int device, const tr_resident_member* members, int
                               void* table_dev, int64_t table_bytes, void* stream);
 
 /*
+ * Scoring sweep: the forward pass and the metrics of many (model, data set) pairs in one launch
+ * (the second half of a hyperparameter grid: every fitted model on its held-out, training and
+ * shuffled data).  No plan is involved.  A member is one pair: X (n_rows, I0, I1) float32 at
+ * x_row_stride floats (0 = I0 * I1), the three factors contiguous in `params` as in
+ * tr_resident_member, the CP component weights, nonneg[3] and the softplus beta / threshold.
+ * Outputs, each of which may be NULL:
+ *   prob    (n_rows, n_classes) float32: softmax(inner(X, B), dim=1), the module's model() output
+ *   pred    int64 [n_rows]: the first index of the row's largest stored prob (numpy's argmax)
+ *   counts  int32 [n_classes * n_classes], row-major counts[pred, true]; needs target.  Zeroed by
+ *           the call on the stream, then summed with integer atomics (exact in any order)
+ *   loss    double [2]: sum_n w[y_n] l_n and sum_n w[y_n], l_n the CrossEntropyLoss of the model()
+ *           output (the double softmax the fits record), w = class_weights or 1; needs target and
+ *           loss_parts, a scratch of 2 * ceil(n_rows / TR_SCORE_ROW_BLOCK) doubles: one workgroup
+ *           scores TR_SCORE_ROW_BLOCK rows, and the workgroups' fp64 partial sums are added in
+ *           block order by a second small kernel
+ * Labels outside [0, n_classes) are the caller's to refuse; such a row is left out of counts and loss.
+ * The envelope: n_classes <= 16, rank <= 16 and the LDS image (the dense P x C coefficient tensor
+ * and the factors) within 160 KiB; it contains every shape for which tr_mnl_resident_max_rows >= 1,
+ * and n_rows is any value >= 1 (X streams from global memory; one call takes at most 4194303 row
+ * blocks over all members, the grid HIP accepts, else TR_E_UNSUPPORTED).  fp32 fmaf sums in one fixed order,
+ * no floating-point atomics: a member's results are bitwise reproducible and independent of the
+ * other members of the table.
+ *   tr_mnl_score_envelope        1 inside the envelope, 0 outside
+ *   tr_score_member_table_bytes  size of the launch's argument table for n_members
+ *   tr_mnl_score_many            checks EVERY member before any device call (NULL X, params or
+ *                                weights, n_rows < 1, a negative stride, counts or loss without
+ *                                target, loss without loss_parts: TR_E_ARG; outside the envelope:
+ *                                TR_E_UNSUPPORTED; tr_last_error() names the member's index) and
+ *                                launches nothing if one fails.  table_host (pinned) and table_dev as
+ *                                in tr_fit_adam_resident_many.  n_members == 0 succeeds.
+ */
+#define TR_SCORE_ROW_BLOCK 256
+
+typedef struct tr_score_member {
+  const float* X;             /* (n_rows, I0, I1) at x_row_stride */
+  const void* target;         /* int64 labels [n_rows], or NULL */
+  const float* params;        /* (I0 + I1 + n_classes) * rank: the three factors, contiguous */
+  const float* weights;       /* [rank] CP component weights */
+  const float* class_weights; /* [n_classes], or NULL (every class at 1) */
+  float* prob;
+  int64_t* pred;
+  int32_t* counts;
+  double* loss;
+  double* loss_parts;         /* scratch, needed with loss */
+  int64_t n_rows, x_row_stride;
+  int64_t I0, I1;
+  int32_t n_classes, rank;
+  int32_t nonneg[3];
+  float softplus_beta, softplus_threshold;
+} tr_score_member;
+
+int tr_mnl_score_envelope(int64_t I0, int64_t I1, int n_classes, int rank);
+int64_t tr_score_member_table_bytes(int n_members);
+int tr_mnl_score_many(int device, const tr_score_member* members, int n_members, void* table_host,
+                      void* table_dev, int64_t table_bytes, void* stream);
+
+/*
  * Fold the NEXT iteration's factor preparation into tr_adam_step: with enable = 1, on a plan
  * that takes the factored multinomial single pass, every tr_adam_step also computes
  * softplus(A_k) and its derivative from the parameters it has just written, and the following

@@ -1341,6 +1341,116 @@ def run_resident_many(dev, members, sync_every=64, trace=None):
     return [int(s) for s in stops], launches
 
 
+SCORE_ROW_BLOCK = _lib.TR_SCORE_ROW_BLOCK  # rows per workgroup of tr_mnl_score_many
+
+
+def score_envelope(I0, I1, n_classes, rank):
+    """tr_mnl_score_envelope: whether tr_mnl_score_many takes this shape (any number of rows)."""
+    return bool(_lib.load().tr_mnl_score_envelope(int(I0), int(I1), int(n_classes), int(rank)))
+
+
+def upload_packed(arrays, dtype, dev):
+    """Host arrays as device tensors through ONE upload: flattened, concatenated, copied to cuda:dev,
+    and returned as views of that buffer in the arrays' shapes."""
+    arrays = [np.ascontiguousarray(a, dtype=dtype) for a in arrays]
+    if not arrays:
+        return []
+    flat = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrays])).to(f"cuda:{dev}")
+    out, o = [], 0
+    for a in arrays:
+        out.append(flat[o:o + a.size].view(a.shape))
+        o += a.size
+    return out
+
+
+_SCORE_TABLES = {}  # device index -> (pinned host table, device table) of run_score_many
+
+
+def run_score_many(dev, members, want, trace=None):
+    """Score many (model, data set) pairs in one call of tr_mnl_score_many.
+
+    `members`: objects with X (N, I0, I1) float32 on cuda:`dev` (samples contiguous, any row stride),
+    y int64 [N] on the device or None, arena and arena_at (a packed float32 tensor and the offset of
+    the member's three factors in it), w [R], cw [C] or None, n_classes, rank, nonneg[3], beta, thr.
+    want = 'predict': returns [(prob (N, C) float32 ndarray, pred (N,) int64 ndarray)], from two
+    downloads.  want = 'score': returns [(sum w[y] l, sum w[y], counts (C, C) int64 ndarray)]; no
+    probabilities are stored, and every member's loss sums and counts come back in one packed buffer:
+    one device-to-host copy, one host sync.  `trace` (a list, for tools/score_many_shapes.py) receives
+    (ms between device events around the call, bytes downloaded)."""
+    if want not in ("predict", "score"):
+        raise ValueError(f"run_score_many: want must be 'predict' or 'score', got {want!r}")
+    lib = _lib.load()
+    M = len(members)
+    if M == 0:
+        return []
+    device = f"cuda:{dev}"
+    rows = [int(mb.X.shape[0]) for mb in members]
+    Cs = [int(mb.n_classes) for mb in members]
+    with torch.cuda.device(dev):
+        nbytes = int(lib.tr_score_member_table_bytes(M))
+        # the table's two buffers are kept per device and grown on demand (pinning memory costs more
+        # than a small call); a call ends in a host sync, so the next one finds them free
+        held = _SCORE_TABLES.get(dev)
+        if held is None or held[0].numel() < nbytes:
+            held = _SCORE_TABLES[dev] = (torch.empty(nbytes, dtype=torch.uint8, pin_memory=True),
+                                         torch.empty(nbytes, dtype=torch.uint8, device=device))
+        table_host, table_dev = held
+        if want == "predict":
+            p_at = np.concatenate([[0], np.cumsum([n * c for n, c in zip(rows, Cs)])])
+            n_at = np.concatenate([[0], np.cumsum(rows)])
+            prob = torch.empty(int(p_at[-1]), dtype=torch.float32, device=device)
+            pred = torch.empty(int(n_at[-1]), dtype=torch.int64, device=device)
+        else:
+            # the packed result: 2 doubles per member, then each member's C * C int32 counts
+            c_at = 16 * M + 4 * np.concatenate([[0], np.cumsum([c * c for c in Cs])])
+            out = torch.empty(int(c_at[-1]), dtype=torch.uint8, device=device)
+            b_at = np.concatenate([[0], np.cumsum([-(-n // SCORE_ROW_BLOCK) for n in rows])])
+            parts = torch.empty(2 * int(b_at[-1]), dtype=torch.float64, device=device)
+    arr = (_lib.ScoreMember * M)()
+    rec = np.frombuffer(arr, dtype=np.dtype(_lib.ScoreMember))  # the same memory, column-wise
+    shapes = np.array([mb.X.shape for mb in members], dtype=np.int64).reshape(M, 3)
+    rec["X"] = [mb.X.data_ptr() for mb in members]
+    rec["params"] = [mb.arena.data_ptr() + 4 * mb.arena_at for mb in members]
+    rec["weights"] = [mb.w.data_ptr() for mb in members]
+    rec["n_rows"], rec["I0"], rec["I1"] = shapes[:, 0], shapes[:, 1], shapes[:, 2]
+    rec["x_row_stride"] = [mb.X.stride(0) if n > 1 else 0 for mb, n in zip(members, rows)]
+    rec["n_classes"], rec["rank"] = Cs, [mb.rank for mb in members]
+    rec["nonneg"] = np.array([[1 if f else 0 for f in mb.nonneg[:3]] for mb in members], dtype=np.int32)
+    rec["softplus_beta"], rec["softplus_threshold"] = [mb.beta for mb in members], [mb.thr for mb in members]
+    if want == "predict":
+        rec["prob"] = prob.data_ptr() + 4 * p_at[:-1]
+        rec["pred"] = pred.data_ptr() + 8 * n_at[:-1]
+    else:
+        rec["target"] = [mb.y.data_ptr() for mb in members]
+        rec["class_weights"] = [0 if mb.cw is None else mb.cw.data_ptr() for mb in members]
+        rec["loss"] = out.data_ptr() + 16 * np.arange(M)
+        rec["counts"] = out.data_ptr() + c_at[:-1]
+        rec["loss_parts"] = parts.data_ptr() + 16 * b_at[:-1]
+    with torch.cuda.device(dev):
+        if trace is not None:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+        check(lib.tr_mnl_score_many(dev, arr, M, ptr(table_host), ptr(table_dev), nbytes, stream_handle(dev)),
+              "tr_mnl_score_many")
+        if trace is not None:
+            ev[1].record()
+        if want == "predict":
+            prob_h, pred_h = prob.cpu().numpy(), pred.cpu().numpy()
+            down = prob_h.nbytes + pred_h.nbytes
+            res = [(prob_h[p_at[j]:p_at[j + 1]].reshape(rows[j], Cs[j]), pred_h[n_at[j]:n_at[j + 1]])
+                   for j in range(M)]
+        else:
+            host = out.cpu().numpy()  # the one device-to-host copy and host sync of the call
+            down = host.nbytes
+            sums = host[:16 * M].view(np.float64).reshape(M, 2)
+            res = [(float(sums[j, 0]), float(sums[j, 1]),
+                    host[c_at[j]:c_at[j + 1]].view(np.int32).reshape(Cs[j], Cs[j]).astype(np.int64))
+                   for j in range(M)]
+        if trace is not None:
+            trace.append((ev[0].elapsed_time(ev[1]), down))
+    return res
+
+
 def _adam_loop(plan, fdt, hp, loss_running, max_iter, tol, verbose_cb, sync_every, chunk, wait=None):
     """The chunked fit loop of run_adam_fit and run_adam_fit_groups: the fit state and the loss
     history, one host sync per chunk, the resume after a failed pass, the verbose callback and the

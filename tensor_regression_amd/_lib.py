@@ -22,6 +22,7 @@ TR_MODEL_CONV_SPECTRAL = 3
 TR_MODEL_CONV_PHASE = 4
 TR_MODEL_CONV_FOURIER = 5
 TR_MAX_FACTORS = 8
+TR_SCORE_ROW_BLOCK = 256  # rows one workgroup of tr_mnl_score_many scores (the header's define)
 KERNEL_KINDS = ["stream_fused", "stream_rows", "stream_cols", "reduce", "mttkrp", "prep", "update"]
 
 _c = ctypes
@@ -39,6 +40,15 @@ class ResidentMember(_c.Structure):
                 ("beta1", _c.c_double), ("beta2", _c.c_double), ("eps", _c.c_double),
                 ("weight_decay", _c.c_double), ("step", _c.c_int64), ("hist_base", _c.c_int64),
                 ("iter", _c.c_int64), ("patience", _c.c_int64), ("tol", _c.c_double)]
+
+
+class ScoreMember(_c.Structure):
+    """`tr_score_member`: one member of tr_mnl_score_many (fields in the header's order)."""
+    _fields_ = [("X", _vp), ("target", _vp), ("params", _vp), ("weights", _vp), ("class_weights", _vp),
+                ("prob", _vp), ("pred", _vp), ("counts", _vp), ("loss", _vp), ("loss_parts", _vp),
+                ("n_rows", _c.c_int64), ("x_row_stride", _c.c_int64), ("I0", _c.c_int64), ("I1", _c.c_int64),
+                ("n_classes", _c.c_int32), ("rank", _c.c_int32), ("nonneg", _c.c_int32 * 3),
+                ("softplus_beta", _c.c_float), ("softplus_threshold", _c.c_float)]
 
 
 # exported symbol -> (restype, argtypes)
@@ -100,6 +110,9 @@ SIGNATURES = {
     "tr_resident_member_table_bytes": (_c.c_int64, [_c.c_int]),
     "tr_fit_adam_resident_many": (_c.c_int, [_c.c_int, _c.POINTER(ResidentMember), _c.c_int, _vp, _vp, _c.c_int64,
                                              _vp]),
+    "tr_mnl_score_envelope": (_c.c_int, [_c.c_int64, _c.c_int64, _c.c_int, _c.c_int]),
+    "tr_score_member_table_bytes": (_c.c_int64, [_c.c_int]),
+    "tr_mnl_score_many": (_c.c_int, [_c.c_int, _c.POINTER(ScoreMember), _c.c_int, _vp, _vp, _c.c_int64, _vp]),
     "tr_plan_set_prepare_next": (_c.c_int, [_vp, _c.c_int]),
     "tr_plan_create_f64": (_c.c_int, [_c.POINTER(_vp), _c.c_int, _c.c_int, _c.POINTER(_c.c_int64), _c.c_int,
                                       _c.c_int64, _c.POINTER(_c.c_int32), _c.c_double, _c.c_double]),

@@ -15,7 +15,7 @@ from ._engine import Plan, as_device_f32, adam_hparams, run_adam_fit
 from .standard_tensor_regression import _plan_for, L2_penalty  # noqa: F401  (L2_penalty re-exported)
 
 __all__ = ["squeeze_integers", "confusion_matrix", "idx_to_oneHot", "make_BcpInit", "non_neg_fn", "model",
-           "L2_penalty", "CP_logistic_regression"]
+           "L2_penalty", "CP_logistic_regression", "predict_many", "score_many"]
 
 
 ####################################
@@ -432,6 +432,295 @@ class CP_logistic_regression():
             axs[ii].set_title(f'factor {ii}')
             axs[ii].plot(val)
         fig.suptitle('components')
+
+
+####################################
+######## Scoring a sweep ###########
+####################################
+
+def _is_host_stream(X):
+    from .util import HostStream
+    return isinstance(X, HostStream)
+
+
+def _per_entry(name, value, M):
+    """None, or a list with one entry per element of `models` (ValueError on another length)."""
+    if value is None:
+        return [None] * M
+    if not isinstance(value, (list, tuple)):
+        raise ValueError(f"{name} must be None or a list with one entry per model, got {type(value).__name__}")
+    if len(value) != M:
+        raise ValueError(f"{name}: a list must hold one entry per model ({M}), got {len(value)}")
+    return list(value)
+
+
+def _host_labels(y):
+    """Labels that live on the host as an int64 ndarray; None for a tensor on a device."""
+    if isinstance(y, torch.Tensor):
+        return None if y.device.type != "cpu" else y.detach().to(torch.long).reshape(-1).numpy()
+    return np.asarray(y).astype(np.int64).reshape(-1)
+
+
+class _ScoreEntry:
+    """One (model, data set) pair of predict_many / score_many."""
+    __slots__ = ("j", "model", "X", "Bcp", "own_Bcp", "N", "dims", "C", "R", "y", "yh", "cw", "arena_at")
+
+
+class _ScoreMember:
+    """One member of _engine.run_score_many."""
+    __slots__ = ("X", "y", "arena", "arena_at", "w", "cw", "n_classes", "rank", "nonneg", "beta", "thr")
+
+
+def _score_entries(who, models, X, y_true, weights, Bcp, need_y):
+    """One record per (model, data set) pair with every argument error of every entry raised.  Nothing
+    here touches a device unless labels already live on one: their range is then read there, all such
+    label tensors of the call in one reduction and one host sync (none for a model's own y that a fit
+    or an earlier call has checked)."""
+    M = len(models)
+    Xs, ys, Bs = _per_entry("X", X, M), _per_entry("y_true", y_true, M), _per_entry("Bcp", Bcp, M)
+    if weights is None or not isinstance(weights, (list, tuple)) or (
+            len(weights) > 0 and np.ndim(weights[0]) == 0 and weights[0] is not None):
+        cws = [weights] * M  # None, or one class-weight vector for every entry
+    else:
+        cws = _per_entry("weights", weights, M)
+    entries = []
+    own = {}       # id(model) -> (Bcp, dims, C, R) of a model's own factors
+    labels = {}    # (id(y), C) -> (n, host labels or None), checked
+    on_device = {}  # (C, device) -> [label tensors on a device, range not yet known]
+    cw_seen = {}   # id(weights entry) -> checked host vector
+    for j, m in enumerate(models):
+        if not isinstance(m, CP_logistic_regression):
+            raise TypeError(f"{who} takes CP_logistic_regression objects of the multinomial modules, "
+                            f"got {type(m).__name__}")
+        e = _ScoreEntry()
+        e.j, e.model = j, m
+        e.X = m.X if Xs[j] is None else Xs[j]
+        e.own_Bcp = Bs[j] is None
+        got = own.get(id(m)) if e.own_Bcp else None
+        if got is None:
+            B = list(m.Bcp if e.own_Bcp else Bs[j])  # (a list of its own: conversions stay out of the caller's)
+            got = (B, [int(A.shape[0]) for A in B[:-1]], int(B[-1].shape[0]), int(B[0].shape[1]))
+            if e.own_Bcp:
+                own[id(m)] = got
+        e.Bcp, e.dims, e.C, e.R = got
+        K = len(e.dims)
+        shape = [int(d) for d in e.X.shape]
+        if len(shape) != K + 1 or shape[1:] != e.dims:
+            raise ValueError(f"Incorrect shapes for inner product along {K} common modes. "
+                             f"tensor_1.shape={shape}, factors={[tuple(A.shape) for A in e.Bcp]}")
+        e.N = shape[0]
+        if e.N < 1:
+            raise ValueError(f"{who}: entry {j} has no samples")
+        e.y = e.yh = e.cw = None
+        if need_y:
+            e.y = y = m.y if ys[j] is None else ys[j]
+            seen = labels.get((id(y), e.C))
+            if seen is None:
+                yh = _host_labels(y)
+                n_y = int(y.numel()) if yh is None else int(yh.size)
+                if n_y > 0 and yh is not None:
+                    ymin, ymax = int(yh.min()), int(yh.max())
+                    if ymin < 0 or ymax >= e.C:
+                        raise IndexError(f"Target {ymax if ymax >= e.C else ymin} is out of bounds.")
+                elif n_y > 0:
+                    c = m._dev_cache  # (_device_data has read the range of the model's own labels)
+                    if not (y is m.y and e.own_Bcp and c is not None and c[2] is y):
+                        on_device.setdefault((e.C, y.device), []).append(y)
+                seen = labels[(id(y), e.C)] = (n_y, yh)
+            if seen[0] != e.N:
+                raise ValueError(f"{who}: entry {j} has {e.N} samples and {seen[0]} labels")
+            e.yh = seen[1]
+            if cws[j] is not None:
+                cw = cw_seen.get(id(cws[j]))
+                if cw is None:
+                    cwh = torch.as_tensor(cws[j], dtype=torch.float32).detach().cpu()
+                    if cwh.ndim != 1 or cwh.numel() != e.C:
+                        raise RuntimeError(f"weight tensor should be defined either for all {e.C} classes or no "
+                                           f"classes but got weight tensor of shape: {list(cwh.shape)}")
+                    cw = cw_seen[id(cws[j])] = cwh.numpy()
+                elif cw.size != e.C:
+                    raise RuntimeError(f"weight tensor should be defined either for all {e.C} classes or no "
+                                       f"classes but got weight tensor of shape: {list(cw.shape)}")
+                e.cw = cw
+        entries.append(e)
+    for (C, _), group in on_device.items():
+        yy = torch.cat([y.reshape(-1) for y in group])
+        ymin, ymax = torch.stack((yy.min(), yy.max())).tolist()
+        if ymin < 0 or ymax >= C:
+            raise IndexError(f"Target {ymax if ymax >= C else ymin} is out of bounds.")
+    return entries
+
+
+def _score_route(entries, who):
+    """(device index, indices scored in the batch, indices handled alone)."""
+    devs, seen = set(), set()
+    for e in entries:
+        key = (id(e.X), id(e.model))
+        if key not in seen:
+            seen.add(key)
+            devs.add(e.X.dev_index if _is_host_stream(e.X) else _engine.compute_device(e.X, e.model.device))
+    if len(devs) != 1:
+        raise ValueError(f"{who}: the models are on different devices ({sorted(devs)})")
+    on = _engine.resident_enabled()
+    batched, alone, inside = [], [], {}
+    for e in entries:
+        ok = False
+        if on and len(e.dims) == 2 and not _is_host_stream(e.X):
+            key = (e.dims[0], e.dims[1], e.C, e.R)
+            ok = inside.get(key)
+            if ok is None:
+                ok = inside[key] = _engine.score_envelope(*key)
+        (batched if ok else alone).append(e.j)
+    return devs.pop(), batched, alone
+
+
+def _score_members(entries, dev, need_y):
+    """The batch's inputs on cuda:dev as run_score_many's members.  Tensors already there are used in
+    place (X at its own row stride); what lives on the host goes up packed, one upload per kind, and an
+    object that several entries share (one model's X, y or factors on four data sets) goes up once."""
+    device = f"cuda:{dev}"
+
+    def place(items, dtype, to_dev):
+        """items: [(key, value)]; returns {key: device tensor}, host values through one packed upload."""
+        out, host = {}, {}
+        for key, v in items:
+            if key in out or key in host:
+                continue
+            if isinstance(v, torch.Tensor) and v.device.type == "cuda":
+                out[key] = to_dev(v)
+            else:
+                host[key] = v.detach().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        for key, t in zip(host, _engine.upload_packed(list(host.values()), dtype, dev)):
+            out[key] = t
+        return out
+
+    for e in entries:
+        if isinstance(e.X, torch.Tensor) and e.X.dtype != torch.float32:
+            raise TypeError(f"the gfx950 path of this model computes in torch.float32; got X of dtype {e.X.dtype}")
+    def rows_in_place(v):  # any base alignment will do: the kernel reads X with 4-byte loads
+        v = v if v.device.index == dev else v.to(device)
+        return v if _engine._rows_contiguous(v) else v.contiguous()
+
+    Xd = place([(id(e.X), e.X) for e in entries], np.float32, rows_in_place)
+    yd = place([(id(e.y), e.y) for e in entries if need_y], np.int64,
+               lambda v: v if (v.dtype == torch.long and v.ndim == 1 and v.is_contiguous() and v.device.index == dev)
+               else v.to(device, torch.long).reshape(-1).contiguous())
+    cwd = place([(id(e.cw), e.cw) for e in entries if e.cw is not None], np.float32, None)
+    wd = place([(id(e.model), e.model.weights) for e in entries], np.float32,
+               lambda v: v.detach().to(device, torch.float32).reshape(-1).contiguous())
+    # every distinct factor list in ONE arena, an offset per entry
+    srcs, at, total = [], {}, 0
+    for e in entries:
+        key = id(e.model) if e.own_Bcp else ("entry", e.j)
+        if key not in at:
+            at[key] = total
+            for f, A in enumerate(e.Bcp):
+                A = A if isinstance(A, torch.Tensor) else torch.as_tensor(np.asarray(A), dtype=torch.float32)
+                if tuple(A.shape) != ((e.dims + [e.C])[f], e.R):
+                    raise ValueError(f"factor {f} has shape {tuple(A.shape)}, expected {((e.dims + [e.C])[f], e.R)}")
+                srcs.append(A.detach().reshape(-1))
+                total += srcs[-1].numel()
+        e.arena_at = at[key]
+    arena = _engine._pack_arena(srcs, total, torch.float32, device)
+    members, nonlin = [], {}
+    for e in entries:
+        nl = nonlin.get(id(e.model))
+        if nl is None:
+            nl = nonlin[id(e.model)] = _engine.nonlin_key(e.model.non_negative, e.model.softplus_kwargs, 3)
+            if wd[id(e.model)].numel() != e.R:
+                raise ValueError(f"the CP component weights hold {wd[id(e.model)].numel()} values, the factors "
+                                 f"have rank {e.R}")
+        mb = _ScoreMember()
+        mb.X, mb.y, mb.arena, mb.arena_at, mb.w = Xd[id(e.X)], yd[id(e.y)] if need_y else None, arena, e.arena_at, \
+            wd[id(e.model)]
+        mb.cw = None if e.cw is None else cwd[id(e.cw)]
+        mb.n_classes, mb.rank, (mb.nonneg, mb.beta, mb.thr) = e.C, e.R, nl
+        members.append(mb)
+    return members
+
+
+def _host_score(prob, pred, y, cw, C):
+    """The metrics of one entry from predict's output, on the host: the double-softmax CrossEntropyLoss
+    sums in float64 and counts[pred, true]."""
+    S = np.asarray(prob, dtype=np.float64)
+    S = S - S.max(axis=1, keepdims=True)
+    l = -(S[np.arange(y.size), y] - np.log(np.exp(S).sum(axis=1)))
+    w = np.ones(y.size) if cw is None else np.asarray(cw, dtype=np.float64)[y]
+    counts = np.zeros((C, C), dtype=np.int64)
+    np.add.at(counts, (pred, y), 1)
+    return float((w * l).sum()), float(w.sum()), counts
+
+
+def _alone_predict(e):
+    return e.model.predict(X=e.X, Bcp=None if e.own_Bcp else list(e.Bcp))
+
+
+def predict_many(models, X=None, Bcp=None, report=None):
+    """`models[j].predict(X=X[j], Bcp=Bcp[j])` of many (model, data set) pairs in one launch: returns
+    [(prob (N_j, C_j) float32 ndarray, pred (N_j,) int64 ndarray)].
+
+    models: CP_logistic_regression objects of either multinomial module; the same object may appear
+    several times (one model on several data sets).  X and Bcp are None (each model's own) or lists
+    with one entry per model, an entry itself None, an ndarray or a tensor (Bcp: a list of factors).
+    An entry inside the kernel's envelope (3-D X, n_classes and rank <= 16, the dense coefficient
+    tensor within one CU's LDS; TR_MNL_RESIDENT not 0) is scored in the batch, every other by its own
+    `predict`.  report (a dict) receives {'batched': indices, 'alone': indices, 'launches': n}."""
+    models = list(models)
+    if report is not None:
+        report.clear()
+        report.update(batched=[], alone=[], launches=0)
+    if not models:
+        return []
+    entries = _score_entries("predict_many", models, X, None, None, Bcp, need_y=False)
+    dev, batched, alone = _score_route(entries, "predict_many")
+    results = [None] * len(models)
+    if batched:
+        got = _engine.run_score_many(dev, _score_members([entries[j] for j in batched], dev, False), "predict")
+        for j, r in zip(batched, got):
+            results[j] = r
+    for j in alone:
+        results[j] = _alone_predict(entries[j])
+    if report is not None:
+        report.update(batched=batched, alone=alone, launches=1 if batched else 0)
+    return results
+
+
+def score_many(models, X=None, y_true=None, weights=None, report=None):
+    """What a hyperparameter grid keeps of every (model, data set) pair, in one launch: returns
+    [{'loss': float, 'acc': float, 'counts': (C, C) int64 ndarray [pred, true], 'cm': ndarray}].
+
+    'loss' is sum w[y] l / sum w[y], the data loss fit_Adam records for that model on that data (the
+    CrossEntropyLoss of the softmax output); weights is None (unweighted), one class-weight vector for
+    all entries or a list of one per entry.  'acc' is trace(counts) / N and 'cm' the column-normalised
+    counts, `confusion_matrix(pred, y)` of this module.  models, X and report as in predict_many;
+    y_true like X (None: each model's own y).  Only the loss sums and the integer counts come back from
+    the device, in one packed copy; no probabilities are downloaded."""
+    models = list(models)
+    if report is not None:
+        report.clear()
+        report.update(batched=[], alone=[], launches=0)
+    if not models:
+        return []
+    entries = _score_entries("score_many", models, X, y_true, weights, None, need_y=True)
+    dev, batched, alone = _score_route(entries, "score_many")
+    raw = [None] * len(models)
+    if batched:
+        got = _engine.run_score_many(dev, _score_members([entries[j] for j in batched], dev, True), "score")
+        for j, r in zip(batched, got):
+            raw[j] = r
+    for j in alone:
+        e = entries[j]
+        prob, pred = _alone_predict(e)
+        yh = e.yh if e.yh is not None else e.y.detach().cpu().numpy().reshape(-1)
+        raw[j] = _host_score(prob, pred, yh, e.cw, e.C)
+    results = []
+    with np.errstate(divide="ignore", invalid="ignore"):  # (a class absent from y: its column is 0 / 0, as the module's)
+        for e, (lsum, wsum, counts) in zip(entries, raw):
+            results.append({"loss": lsum / wsum, "acc": float(np.trace(counts) / e.N), "counts": counts,
+                            "cm": counts / np.sum(counts, axis=0)[None, :]})
+    if report is not None:
+        report.update(batched=batched, alone=alone, launches=1 if batched else 0)
+    return results
 
 
 class _Verbose:

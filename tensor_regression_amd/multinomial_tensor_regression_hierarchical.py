@@ -32,10 +32,11 @@ from . import _engine
 from ._engine import adam_hparams, run_adam_fit_groups
 from . import multinomial_tensor_regression as _mnl
 from .multinomial_tensor_regression import (squeeze_integers, confusion_matrix, idx_to_oneHot,  # noqa: F401
-                                            make_BcpInit, non_neg_fn, model, L2_penalty, _Verbose)
+                                            make_BcpInit, non_neg_fn, model, L2_penalty, _Verbose,
+                                            predict_many, score_many)
 
 __all__ = ["squeeze_integers", "confusion_matrix", "idx_to_oneHot", "make_BcpInit", "non_neg_fn", "model",
-           "L2_penalty", "CP_logistic_regression", "fit_Adam_many"]
+           "L2_penalty", "CP_logistic_regression", "fit_Adam_many", "predict_many", "score_many"]
 
 N_GROUPS = 3  # hierarchical…py:436-440: Bcp[0], Bcp[1], Bcp[2]
 
