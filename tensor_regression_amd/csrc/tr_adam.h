@@ -5,7 +5,7 @@
 //
 // The Adam helpers hold arithmetic only and are compiled without contraction (the pragma travels
 // with the inlined instructions).  The caller keeps vm = fmaxf(vm, vv), every store and the order of
-// the stores, its loops, and the wave butterfly (tr_wave_allreduce) between norm_add and
+// the stores, its loops, and the wave butterfly (wv_allreduce) between norm_add and
 // norm_finish: k_update sits at the SGPR ceiling (106, spilling to lanes), and with these pieces at
 // the call site its gfx950 code is instruction for instruction what it was when the step was
 // written out in the kernel.  (k64_update, tr_fp64.hip, is compiled with contraction on and keeps
@@ -35,15 +35,6 @@ __device__ __forceinline__ float adam_param(float p, float mm, float second, flo
   return p + (-step_size) * (mm / denom);
 }
 
-// The factor of arena element e (off[] ascending; nf a literal where the kernel fixes it).
-__device__ __forceinline__ int factor_of(const FactorSet& fs, int nf, int64_t e) {
-  int f = 0;
-#pragma unroll
-  for (int g = 1; g < TR_MAXF; ++g)
-    if (g < nf && e >= fs.off[g]) f = g;
-  return f;
-}
-
 // ||A_f||_F^2 of every factor (raw parameters), one element of this thread's share: a thread sums the
 // elements k = t (mod 1024) in increasing k, the factor's accumulator selected without a branch.
 __device__ __forceinline__ void norm_add(const FactorSet& fs, int nf, int64_t k, float a, float (&accn)[TR_MAXF]) {
@@ -52,7 +43,7 @@ __device__ __forceinline__ void norm_add(const FactorSet& fs, int nf, int64_t k,
   for (int g = 0; g < TR_MAXF; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
 }
 
-// After the wave butterfly of every accumulator (tr_wave_allreduce, lane 0 to wsum[f * 16 + wave]) and
+// After the wave butterfly of every accumulator (wv_allreduce, lane 0 to wsum[f * 16 + wave]) and
 // a barrier, thread f < nf: the wave-order sum of the NWV wave sums, ||A_f|| and the L2 coefficient,
 // d/dA lambda ||A|| = (lambda / (2 ||A||)) * (2 A); a barrier follows.
 template <int NWV>

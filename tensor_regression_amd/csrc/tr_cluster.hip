@@ -35,13 +35,6 @@ namespace {
 constexpr int CL_T = 512;               // threads per workgroup
 constexpr int CL_NW = CL_T / TR_WAVE;   // 8 waves
 constexpr int CL_TC = CL_T - TR_WAVE;   // 448 streaming threads (waves 1..7)
-
-__device__ __forceinline__ void cl_barrier() {
-  // LDS-only barrier: the streaming waves' next-row X loads stay in flight across it.
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 }  // namespace
 
 template <int CH>
@@ -96,7 +89,7 @@ __global__ __launch_bounds__(CL_T) void k_linear_cluster(
         const_cast<char*>(Xb + row_of(i) * xld * 4), (short)0, (int)slice_bytes, 0x00020000);
 #pragma unroll
     for (int c = 0; c < CH; ++c) {  // beyond the slice the range check returns zeros
-      const tr_f4 v = __builtin_bit_cast(tr_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, c * CL_TC * 16, 2));
+      const wv_f4 v = __builtin_bit_cast(wv_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, c * CL_TC * 16, 2));
       x[c] = make_float4(v.x, v.y, v.z, v.w);
     }
   };
@@ -114,10 +107,10 @@ __global__ __launch_bounds__(CL_T) void k_linear_cluster(
       float d = 0.f;
 #pragma unroll
       for (int c = 0; c < CH; ++c) d = tr_dot4(xc[c], lds_b[ct + c * CL_TC], d);
-      d = tr_wave_allreduce(d);
+      d = wv_allreduce(d);
       if (lane == 0) red[par * CL_NW + wv] = d;
     }
-    cl_barrier();
+    wv_barrier();
     if (wv == 0) {
       float part = 0.f;
 #pragma unroll
@@ -154,7 +147,7 @@ __global__ __launch_bounds__(CL_T) void k_linear_cluster(
       if (dead) dot = __builtin_nanf("");
       if (lane == 0) tot[par] = dot;
     }
-    cl_barrier();
+    wv_barrier();
     if (wv > 0) {
       const float dot = tot[par];
       const float e = dot + bias - y[row_of(i)];

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tr_wave.h"
+
 #define TR_WAVE 64
 #define TR_MAXF 8     // max factors (modes of the dense coefficient tensor)
 #define TR_MAXR 1024  // max CP rank (MTTKRP tiles ranks by 64; the reference has no limit)
@@ -46,39 +48,25 @@ __device__ __forceinline__ float tr_softplus_grad(float a, float beta, float thr
   const float z = expf(ab);
   return z / (z + 1.0f);
 }
+// the same in double (the float64 pipeline, tr_fp64.hip)
+__device__ __forceinline__ double d_softplus(double a, double beta, double thr) {
+  const double ab = a * beta;
+  return ab > thr ? a : log1p(exp(ab)) / beta;
+}
+__device__ __forceinline__ double d_softplus_grad(double a, double beta, double thr) {
+  const double ab = a * beta;
+  if (ab > thr) return 1.0;
+  const double z = exp(ab);
+  return z / (z + 1.0);
+}
 
-// All-reduce across the 64 lanes of a wave without address VGPRs: ds_swizzle xor-butterfly
-// inside each 32-lane half (bit-mask mode, offset = xor<<10 | and 0x1F), then the two half
-// sums through readlane.  Commutativity of IEEE addition makes every lane of a half hold the
-// bitwise-identical value, so the result is the same scalar in every lane (deterministic).
-template <int PATTERN>
-__device__ __forceinline__ float tr_swz_xor(float v) {
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), PATTERN));
-}
-__device__ __forceinline__ float tr_wave_allreduce(float v) {
-  v += tr_swz_xor<0x401F>(v);  // xor 16
-  v += tr_swz_xor<0x201F>(v);  // xor 8
-  v += tr_swz_xor<0x101F>(v);  // xor 4
-  v += tr_swz_xor<0x081F>(v);  // xor 2
-  v += tr_swz_xor<0x041F>(v);  // xor 1
-  const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-  const float b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-  return a + b;
-}
-__device__ __forceinline__ float tr_wave_allreduce_max(float v) {
-  v = fmaxf(v, tr_swz_xor<0x401F>(v));
-  v = fmaxf(v, tr_swz_xor<0x201F>(v));
-  v = fmaxf(v, tr_swz_xor<0x101F>(v));
-  v = fmaxf(v, tr_swz_xor<0x081F>(v));
-  v = fmaxf(v, tr_swz_xor<0x041F>(v));
-  const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-  const float b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-  return fmaxf(a, b);
-}
-__device__ __forceinline__ double tr_wave_allreduce_d(double v) {
+// The factor of arena element e (off[] ascending; nf a literal where the kernel fixes it).
+__device__ __forceinline__ int factor_of(const FactorSet& fs, int nf, int64_t e) {
+  int f = 0;
 #pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  for (int g = 1; g < TR_MAXF; ++g)
+    if (g < nf && e >= fs.off[g]) f = g;
+  return f;
 }
 
 __device__ __forceinline__ float tr_dot4(const float4 a, const float4 b, float acc) {
@@ -96,9 +84,8 @@ __device__ __forceinline__ void tr_axpy4(float s, const float4 x, float4& acc) {
 }
 
 // Non-temporal 16-B load for the once-per-pass X stream (X >> 256 MiB Infinity Cache).
-typedef float tr_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 tr_ld_stream(const float4* p) {
-  const tr_f4 v = __builtin_nontemporal_load(reinterpret_cast<const tr_f4*>(p));
+  const wv_f4 v = __builtin_nontemporal_load(reinterpret_cast<const wv_f4*>(p));
   return make_float4(v.x, v.y, v.z, v.w);
 }
 

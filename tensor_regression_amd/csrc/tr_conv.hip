@@ -43,14 +43,6 @@ constexpr int QP = CONV_MAXR + 1;          // LDS pitch of a q / dq row
 constexpr int DZ_FLOATS = 4 * 64 * CONV_KC;  // four wave-private dz tiles
 constexpr int LDS_BUDGET_FLOATS = 38912;     // 152 KiB of the CU's 160 KiB
 
-__device__ __forceinline__ void wave_lds_sync() {
-  // the wave's own LDS writes before its lanes read each other's (one wave executes in lockstep;
-  // the fences keep the compiler from moving the accesses across)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // z[0..15] of one (time, column): the slab column at xp, the group's kernel rows at kp
 __device__ __forceinline__ void conv_z(const float* __restrict__ xp, const float* __restrict__ kp, int W,
                                        float (&z)[CONV_KC]) {
@@ -151,7 +143,7 @@ __device__ __forceinline__ void conv_b_group(const float* sX, const float* sDQ, 
 #pragma unroll
       for (int k4 = 0; k4 < CONV_KC / 4; ++k4)
         wr[k4] = make_float4(dz[4 * k4], dz[4 * k4 + 1], dz[4 * k4 + 2], dz[4 * k4 + 3]);
-      wave_lds_sync();
+      wv_lds_sync();
       for (int tt = ts * WL; tt < ts * WL + WL; ++tt) {
         float dzv[CONV_KC];
         const float4* rd = reinterpret_cast<const float4*>(myDZ + tt * CONV_KC);
@@ -174,11 +166,11 @@ __device__ __forceinline__ void conv_b_group(const float* sX, const float* sDQ, 
           }
         }
       }
-      wave_lds_sync();
+      wv_lds_sync();
     }
 #pragma unroll
     for (int j = 0; j < RPG; ++j) {
-      const float s = tr_wave_allreduce(bd[j]);
+      const float s = wv_allreduce(bd[j]);
       if (lane == j && j < nr) slabBd[(int64_t)dl * R + j] += s;
     }
   }
@@ -327,7 +319,7 @@ __global__ __launch_bounds__(CONV_TT) void k_conv(ConvGeom g, const float* __res
   }
   if (TRAIN) {
     __shared__ double wl[CONV_TT / 64];
-    const double s = tr_wave_allreduce_d(lossacc);
+    const double s = wv_allreduce_d(lossacc);
     if ((tid & 63) == 0) wl[tid >> 6] = s;
     __syncthreads();
     if (tid == 0) dpart[blockIdx.x] = (wl[0] + wl[1]) + (wl[2] + wl[3]);
@@ -407,7 +399,7 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
   for (int64_t k = t; k < nfe; k += 1024) norm_add(fs, 4, k, params[k], accn);
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
-    const float r = tr_wave_allreduce(accn[f]);
+    const float r = wv_allreduce(accn[f]);
     if (lane == 0) wsum[f * 16 + q] = r;
   }
   const int ord = sm.order, Wq = W + ord, Rk = Rn + RsK;
@@ -431,7 +423,7 @@ __global__ __launch_bounds__(1024) void k_update_conv(FactorSet fs, int n_bias, 
     }
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
-      const float r = tr_wave_allreduce(accs[f]);
+      const float r = wv_allreduce(accs[f]);
       if (lane == 0) ssum[f * 16 + q] = r;
     }
   }

@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void k_spec_pen(int64_t FsN, float coef, const
       dM[e] = coef * (r / den);
     }
   }
-  const double s = tr_wave_allreduce_d(acc);
+  const double s = wv_allreduce_d(acc);
   if ((tid & 63) == 0) wl[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) ppart[blockIdx.x] = (wl[0] + wl[1]) + (wl[2] + wl[3]);

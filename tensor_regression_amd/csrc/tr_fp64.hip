@@ -25,36 +25,13 @@
 
 namespace tr {
 
-__device__ __forceinline__ double d_softplus(double a, double beta, double thr) {
-  const double ab = a * beta;
-  return ab > thr ? a : log1p(exp(ab)) / beta;
-}
-__device__ __forceinline__ double d_softplus_grad(double a, double beta, double thr) {
-  const double ab = a * beta;
-  if (ab > thr) return 1.0;
-  const double z = exp(ab);
-  return z / (z + 1.0);
-}
-__device__ __forceinline__ double d_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int d_factor_of(const FactorSet& fs, int64_t e) {
-  int f = 0;
-#pragma unroll
-  for (int g = 1; g < TR_MAXF; ++g)
-    if (g < fs.nf && e >= fs.off[g]) f = g;
-  return f;
-}
-
 __global__ __launch_bounds__(256) void k64_prep(FactorSet fs, const double* __restrict__ params, double beta,
                                                 double thr, double* __restrict__ phi, double* __restrict__ dphi,
                                                 const int32_t* __restrict__ stop) {
   if (stop != nullptr && *stop != 0) return;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < fs.nfelem; e += (int64_t)gridDim.x * blockDim.x) {
     const double a = params[e];
-    if (fs.nonneg[d_factor_of(fs, e)]) {
+    if (fs.nonneg[factor_of(fs, fs.nf, e)]) {
       phi[e] = d_softplus(a, beta, thr);
       dphi[e] = d_softplus_grad(a, beta, thr);
     } else {
@@ -115,7 +92,7 @@ __global__ __launch_bounds__(256) void k64_rows(const double* __restrict__ X, in
       a1 = fma(xr[p + 64], B[p + 64], a1);
     }
     if (p < P) a0 = fma(xr[p], B[p], a0);
-    const double yh = d_wave_sum(a0 + a1) + bias;
+    const double yh = wv_allreduce_d(a0 + a1) + bias;
     if (PRED) {
       if (lane == 0) out[n] = yh;
       continue;
@@ -173,8 +150,8 @@ __global__ __launch_bounds__(256) void k64_reduce(const double* __restrict__ par
       s0 += dpart[2 * i];
       s1 += dpart[2 * i + 1];
     }
-    s0 = d_wave_sum(s0);
-    s1 = d_wave_sum(s1);
+    s0 = wv_allreduce_d(s0);
+    s1 = wv_allreduce_d(s1);
     const int q = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
       red[0][q] = s0;
@@ -236,7 +213,7 @@ __global__ __launch_bounds__(256) void k64_mttkrp(FactorSet fs, const double* __
 #pragma unroll
   for (int r = 0; r < RT; ++r) {
     if (r < Rt) {
-      const double v = d_wave_sum(acc[r]);
+      const double v = wv_allreduce_d(acc[r]);
       if (lane == 0) red[q][r] = v;
     }
   }
@@ -269,7 +246,7 @@ __global__ __launch_bounds__(1024) void k64_update(FactorSet fs, int n_bias, dou
     for (int f = 0; f < TR_MAXF; ++f) accn[f] = 0.0;
     for (int64_t k = t; k < nfe; k += blockDim.x) {
       const double a = params[k];
-      const int f = d_factor_of(fs, k);
+      const int f = factor_of(fs, fs.nf, k);
 #pragma unroll
       for (int g = 0; g < TR_MAXF; ++g)
         if (g == f) accn[g] = fma(a, a, accn[g]);
@@ -277,7 +254,7 @@ __global__ __launch_bounds__(1024) void k64_update(FactorSet fs, int n_bias, dou
 #pragma unroll
     for (int f = 0; f < TR_MAXF; ++f)
       if (f < fs.nf) {
-        const double s = d_wave_sum(accn[f]);
+        const double s = wv_allreduce_d(accn[f]);
         if (lane == 0) wsum[f * 16 + q] = s;
       }
     __syncthreads();
@@ -292,7 +269,7 @@ __global__ __launch_bounds__(1024) void k64_update(FactorSet fs, int n_bias, dou
   for (int64_t e = t; e < np; e += blockDim.x) {
     double g = grad[e];
     double p = params[e];
-    if (e < nfe) g = g + (lam / (2.0 * norms[d_factor_of(fs, e)])) * (2.0 * p);
+    if (e < nfe) g = g + (lam / (2.0 * norms[factor_of(fs, fs.nf, e)])) * (2.0 * p);
     if (ua.mode == 1) {
       grad_total_out[e] = g;
       continue;

@@ -31,7 +31,7 @@ namespace tr {
 // ------------------------------------------------------------------------------------------
 #define TR_X_AUX 2  // buffer-load cache-policy bits (2 = nt)
 __device__ __forceinline__ float4 ldx(const float4* p) {
-  const tr_f4 v = __builtin_nontemporal_load(reinterpret_cast<const tr_f4*>(p));
+  const wv_f4 v = __builtin_nontemporal_load(reinterpret_cast<const wv_f4*>(p));
   return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ float ldx(const float* p) { return __builtin_nontemporal_load(p); }
@@ -101,10 +101,7 @@ __global__ __launch_bounds__(256) void k_prep_factors(FactorSet fs, const float*
   if (stop != nullptr && *stop != 0) return;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= fs.nfelem) return;
-  int f = 0;
-#pragma unroll
-  for (int g = 1; g < TR_MAXF; ++g)
-    if (g < fs.nf && e >= fs.off[g]) f = g;
+  const int f = factor_of(fs, fs.nf, e);
   const float a = params[e];
   if (fs.nonneg[f]) {
     phi[e] = tr_softplus(a, beta, thr);
@@ -121,14 +118,6 @@ __global__ __launch_bounds__(256) void k_prep_factors(FactorSet fs, const float*
 // applies softplus there (sum_f I_f * R floats); workgroup 0 also publishes Phi and softplus'
 // for the gradient kernels.  Factor sets too large for LDS fall back to k_prep_factors + global.
 // ==========================================================================================
-__device__ __forceinline__ int tr_factor_of(const FactorSet& fs, int64_t e) {
-  int f = 0;
-#pragma unroll
-  for (int g = 1; g < TR_MAXF; ++g)
-    if (g < fs.nf && e >= fs.off[g]) f = g;
-  return f;
-}
-
 __global__ __launch_bounds__(256) void k_build_dense(FactorSet fs, const float* __restrict__ params,
                                                      float beta, float thr, float* __restrict__ phi,
                                                      float* __restrict__ dphi, const float* __restrict__ w,
@@ -145,7 +134,7 @@ __global__ __launch_bounds__(256) void k_build_dense(FactorSet fs, const float* 
       if (g < fs.nf && fs.nonneg[g]) nnmask |= 1u << g;
     auto stage = [&](int64_t k, float a) {
       float v = a, d = 1.0f;
-      if ((nnmask >> tr_factor_of(fs, k)) & 1u) {
+      if ((nnmask >> factor_of(fs, fs.nf, k)) & 1u) {
         v = tr_softplus(a, beta, thr);
         d = tr_softplus_grad(a, beta, thr);
       }
@@ -282,7 +271,7 @@ __global__ __launch_bounds__(T) void k_linear_fused(
         const_cast<char*>(base), (short)0, (int)row_bytes, 0x00020000);
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
-      const tr_f4 v = __builtin_bit_cast(tr_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, c * T * 16, TR_X_AUX));
+      const wv_f4 v = __builtin_bit_cast(wv_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, c * T * 16, TR_X_AUX));
       x[c] = make_float4(v.x, v.y, v.z, v.w);
     }
   };
@@ -290,7 +279,7 @@ __global__ __launch_bounds__(T) void k_linear_fused(
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < CH; ++c) s = tr_dot4(x[c], lds_b[t + c * T], s);
-    s = tr_wave_allreduce(s);
+    s = wv_allreduce(s);
     if (lane == 0) red[par * NW + wv] = s;
     __syncthreads();
     float dot = 0.f;
@@ -395,17 +384,17 @@ __global__ __launch_bounds__(256) void k_linear_packed(
       const int nrec = rin[u] > 0 ? (int)((int64_t)(rin[u] - 1) * xld * 4 + P * 4) : 0;
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<char*>(Xb + (k < nb ? fr[u] : 0) * xld * 4), (short)0, nrec, 0x00020000);
-      const tr_f4 v = __builtin_bit_cast(tr_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, TR_X_AUX));
+      const wv_f4 v = __builtin_bit_cast(wv_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, TR_X_AUX));
       x[u] = make_float4(m0 ? v.x : 0.f, m1 ? v.y : 0.f, m2 ? v.z : 0.f, m3 ? v.w : 0.f);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float s = tr_dot4(x[u], b, 0.f);
-      if (PQ >= 32) s += tr_swz_xor<0x401F>(s);
-      if (PQ >= 16) s += tr_swz_xor<0x201F>(s);
-      if (PQ >= 8) s += tr_swz_xor<0x101F>(s);
-      if (PQ >= 4) s += tr_swz_xor<0x081F>(s);
-      if (PQ >= 2) s += tr_swz_xor<0x041F>(s);
+      if (PQ >= 32) s += wv_swz<0x401F>(s);
+      if (PQ >= 16) s += wv_swz<0x201F>(s);
+      if (PQ >= 8) s += wv_swz<0x101F>(s);
+      if (PQ >= 4) s += wv_swz<0x081F>(s);
+      if (PQ >= 2) s += wv_swz<0x041F>(s);
       const bool valid = seg < rin[u];
       const float e = valid ? s + bias - y[fr[u] + seg] : 0.f;
       const float r = e * scale;
@@ -424,8 +413,8 @@ __global__ __launch_bounds__(256) void k_linear_packed(
     g.z += __shfl_xor(g.z, o, TR_WAVE);
     g.w += __shfl_xor(g.w, o, TR_WAVE);
   }
-  sse = tr_wave_allreduce_d(sse);
-  rsum = tr_wave_allreduce_d(rsum);
+  sse = wv_allreduce_d(sse);
+  rsum = wv_allreduce_d(rsum);
   if (seg == 0) sg[wv][q] = g;
   if (lane == 0) {
     sd[wv][0] = sse;
@@ -549,7 +538,7 @@ __global__ __launch_bounds__(256) void k_rows(
 #pragma unroll
   for (int r = 0; r < RB; ++r)
 #pragma unroll
-    for (int c = 0; c < C; ++c) acc[r][c] = tr_wave_allreduce(acc[r][c]);
+    for (int c = 0; c < C; ++c) acc[r][c] = wv_allreduce(acc[r][c]);
 
   if (MODE == MODE_MNL_LOGITS) {  // one class tile of the logits, row stride ldo
 #pragma unroll
@@ -666,27 +655,6 @@ __global__ __launch_bounds__(256) void k_rows(
 // both operands, so the k order is permuted consistently.  Accumulator layout: class = l&15,
 // row = 4*(l>>4) + reg.  Class reductions are 16-lane swizzle butterflies (deterministic).
 // ==========================================================================================
-template <int PATTERN>
-__device__ __forceinline__ float tr_swz(float v) {
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), PATTERN));
-}
-__device__ __forceinline__ float tr_sum16(float v) {
-  v += tr_swz<0x201F>(v);  // xor 8
-  v += tr_swz<0x101F>(v);  // xor 4
-  v += tr_swz<0x081F>(v);  // xor 2
-  v += tr_swz<0x041F>(v);  // xor 1
-  return v;
-}
-__device__ __forceinline__ float tr_max16(float v) {
-  v = fmaxf(v, tr_swz<0x201F>(v));
-  v = fmaxf(v, tr_swz<0x101F>(v));
-  v = fmaxf(v, tr_swz<0x081F>(v));
-  v = fmaxf(v, tr_swz<0x041F>(v));
-  return v;
-}
-
-typedef float tr_f32x4 __attribute__((ext_vector_type(4)));
-
 template <int MODE, int RT>
 __global__ __launch_bounds__(256) void k_rows_mfma(
     const float* __restrict__ X, int64_t N, int64_t P, int64_t xld, const float* __restrict__ Bt, int C,
@@ -725,33 +693,33 @@ __global__ __launch_bounds__(256) void k_rows_mfma(
   // chain over all P/4 MFMAs (round 2) left Z 6.5e-5 from exact at P = 8192, |Z| = 58
   // (mnl_duo_t), 2x the probability error of the reference's own blocked fp32 GEMM; this order
   // is 6.9e-6 (emulated).  Independent chains also keep back-to-back MFMAs independent.
-  tr_f32x4 ac[RT][8], acc[RT];
+  wv_f4 ac[RT][8], acc[RT];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
-    acc[rt] = tr_f32x4{0.f, 0.f, 0.f, 0.f};
+    acc[rt] = wv_f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int m = 0; m < 8; ++m) ac[rt][m] = tr_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < 8; ++m) ac[rt][m] = wv_f4{0.f, 0.f, 0.f, 0.f};
   }
   auto fold = [&]() {
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
       acc[rt] += ((ac[rt][0] + ac[rt][1]) + (ac[rt][2] + ac[rt][3])) + ((ac[rt][4] + ac[rt][5]) + (ac[rt][6] + ac[rt][7]));
 #pragma unroll
-      for (int m = 0; m < 8; ++m) ac[rt][m] = tr_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int m = 0; m < 8; ++m) ac[rt][m] = wv_f4{0.f, 0.f, 0.f, 0.f};
     }
   };
   const int nsteps = (int)(P / 32);
   auto step = [&](const float4(&xa)[RT], const float4(&xb)[RT], const float4 ba, const float4 bb) {
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-      ac[rt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt].x, ba.x, ac[rt][0], 0, 0, 0);
-      ac[rt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt].y, ba.y, ac[rt][1], 0, 0, 0);
-      ac[rt][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt].z, ba.z, ac[rt][2], 0, 0, 0);
-      ac[rt][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt].w, ba.w, ac[rt][3], 0, 0, 0);
-      ac[rt][4] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[rt].x, bb.x, ac[rt][4], 0, 0, 0);
-      ac[rt][5] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[rt].y, bb.y, ac[rt][5], 0, 0, 0);
-      ac[rt][6] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[rt].z, bb.z, ac[rt][6], 0, 0, 0);
-      ac[rt][7] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[rt].w, bb.w, ac[rt][7], 0, 0, 0);
+      ac[rt][0] = wv_mfma_16x16x4(xa[rt].x, ba.x, ac[rt][0]);
+      ac[rt][1] = wv_mfma_16x16x4(xa[rt].y, ba.y, ac[rt][1]);
+      ac[rt][2] = wv_mfma_16x16x4(xa[rt].z, ba.z, ac[rt][2]);
+      ac[rt][3] = wv_mfma_16x16x4(xa[rt].w, ba.w, ac[rt][3]);
+      ac[rt][4] = wv_mfma_16x16x4(xb[rt].x, bb.x, ac[rt][4]);
+      ac[rt][5] = wv_mfma_16x16x4(xb[rt].y, bb.y, ac[rt][5]);
+      ac[rt][6] = wv_mfma_16x16x4(xb[rt].z, bb.z, ac[rt][6]);
+      ac[rt][7] = wv_mfma_16x16x4(xb[rt].w, bb.w, ac[rt][7]);
     }
   };
   int st = 0;
@@ -800,18 +768,18 @@ __global__ __launch_bounds__(256) void k_rows_mfma(
     for (int reg = 0; reg < 4; ++reg) {
       const int64_t row = row0 + rt * 16 + 4 * g + reg;
       const float z = cls_ok ? acc[rt][reg] : NEG;
-      const float mx = tr_max16(z);
+      const float mx = wv_swz_max16(z);
       const float ez = cls_ok ? expf(z - mx) : 0.f;
-      const float sum = tr_sum16(ez);
+      const float sum = wv_swz_sum16(ez);
       const float S = ez * (1.0f / sum);
       if (MODE == MODE_MNL_PRED) {
         if (cls_ok && row < N) out[row * ldo + i] = S;
         continue;
       }
       // CrossEntropyLoss(weight) on the probabilities S (double softmax)
-      const float m2 = tr_max16(cls_ok ? S : NEG);
+      const float m2 = wv_swz_max16(cls_ok ? S : NEG);
       const float q = cls_ok ? expf(S - m2) : 0.f;
-      const float s2 = tr_sum16(q);
+      const float s2 = wv_swz_sum16(q);
       const float lse = logf(s2);
       const bool valid = row < N;
       const int64_t yl = valid ? lab[row] : -1;
@@ -819,12 +787,12 @@ __global__ __launch_bounds__(256) void k_rows_mfma(
       const bool is_y = cls_ok && (int64_t)i == yl;
       if (is_y) lsum += (double)cw * (double)(-((S - m2) - lse));
       const float dS = cls_ok ? (q * (1.0f / s2) - (is_y ? 1.0f : 0.0f)) * (cw * scale) : 0.f;
-      const float dot = tr_sum16(dS * S);
+      const float dot = wv_swz_sum16(dS * S);
       if (cls_ok && valid) out[row * ldo + i] = S * (dS - dot);
     }
   }
   if (MODE == MODE_MNL_TRAIN) {
-    lsum = tr_wave_allreduce_d(lsum);
+    lsum = wv_allreduce_d(lsum);
     if (lane == 0) {
       dpart[2 * gw] = lsum;
       dpart[2 * gw + 1] = 0.0;
@@ -854,10 +822,10 @@ __global__ __launch_bounds__(256) void k_softmax_rows(float* __restrict__ Z, int
     float* z = Z + row * C;
     float mx = NEG;
     for (int c = lane; c < C; c += TR_WAVE) mx = fmaxf(mx, z[c]);
-    mx = tr_wave_allreduce_max(mx);
+    mx = wv_allreduce_max(mx);
     float sum = 0.f;
     for (int c = lane; c < C; c += TR_WAVE) sum += expf(z[c] - mx);
-    sum = tr_wave_allreduce(sum);
+    sum = wv_allreduce(sum);
     const float inv = 1.0f / sum;
     if (MODE == MODE_MNL_PRED) {
       for (int c = lane; c < C; c += TR_WAVE) out[row * C + c] = expf(z[c] - mx) * inv;
@@ -865,10 +833,10 @@ __global__ __launch_bounds__(256) void k_softmax_rows(float* __restrict__ Z, int
     }
     float m2 = NEG;
     for (int c = lane; c < C; c += TR_WAVE) m2 = fmaxf(m2, expf(z[c] - mx) * inv);
-    m2 = tr_wave_allreduce_max(m2);
+    m2 = wv_allreduce_max(m2);
     float s2 = 0.f;
     for (int c = lane; c < C; c += TR_WAVE) s2 += expf(expf(z[c] - mx) * inv - m2);
-    s2 = tr_wave_allreduce(s2);
+    s2 = wv_allreduce(s2);
     const float lse = logf(s2), inv2 = 1.0f / s2;
     const int64_t yl = lab[row];
     const float cw = class_w[yl];
@@ -880,7 +848,7 @@ __global__ __launch_bounds__(256) void k_softmax_rows(float* __restrict__ Z, int
       dot = fmaf(dS, S, dot);
       if (c == yl) lsum += (double)cw * (double)(-((S - m2) - lse));
     }
-    dot = tr_wave_allreduce(dot);
+    dot = wv_allreduce(dot);
     for (int c = lane; c < C; c += TR_WAVE) {
       const float S = expf(z[c] - mx) * inv;
       const float dS = (expf(S - m2) * inv2 - (c == yl ? 1.0f : 0.0f)) * gsc;
@@ -888,7 +856,7 @@ __global__ __launch_bounds__(256) void k_softmax_rows(float* __restrict__ Z, int
     }
   }
   if (MODE == MODE_MNL_TRAIN) {
-    lsum = tr_wave_allreduce_d(lsum);
+    lsum = wv_allreduce_d(lsum);
     if (lane == 0) {
       dpart[2 * gw] = lsum;
       dpart[2 * gw + 1] = 0.0;
@@ -1068,8 +1036,8 @@ __global__ __launch_bounds__(1024) void k_reduce_slabs(const float* __restrict__
       s0 += dpart[2 * i];
       s1 += dpart[2 * i + 1];
     }
-    s0 = tr_wave_allreduce_d(s0);
-    s1 = tr_wave_allreduce_d(s1);
+    s0 = wv_allreduce_d(s0);
+    s1 = wv_allreduce_d(s1);
     if (lane == 0) {
       dred[0][q] = s0;
       dred[1][q] = s1;
@@ -1129,7 +1097,7 @@ __global__ __launch_bounds__(256) void k_mttkrp(FactorSet fs, const float* __res
   const float* F = phi;
   if constexpr (USE_LDS) {
     for (int k = threadIdx.x; k < (int)fs.nfelem; k += blockDim.x) {
-      const int g = tr_factor_of(fs, k);
+      const int g = factor_of(fs, fs.nf, k);
       int rows_before = 0;
       for (int h = 0; h < g; ++h) rows_before += (int)fs.dim[h];
       const int within = k - (int)fs.off[g];
@@ -1224,7 +1192,7 @@ __global__ __launch_bounds__(256) void k_mttkrp(FactorSet fs, const float* __res
 #pragma unroll
   for (int r = 0; r < RMAX; ++r) {
     if (r < Rt) {
-      const float v = tr_wave_allreduce(acc[r]);
+      const float v = wv_allreduce(acc[r]);
       if (lane == 0) red[q][r] = v;
     }
   }

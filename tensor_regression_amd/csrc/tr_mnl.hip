@@ -61,92 +61,6 @@ namespace tr {
 namespace {
 constexpr int MN_NW = 8;
 constexpr int MN_T = MN_NW * TR_WAVE;
-typedef float mn_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ mn_f32x4 mfma_4x4(float a, float b, mn_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// 16-lane row reductions by DPP: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror,
-// row_mirror.  Each step adds the same two operands in every lane of a pair, so all 16 lanes
-// end with the bitwise-identical value.
-__device__ __forceinline__ float row_sum16(float v) {
-  v += dpp_f<0xB1>(v);
-  v += dpp_f<0x4E>(v);
-  v += dpp_f<0x141>(v);
-  v += dpp_f<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ float row_max16(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  v = fmaxf(v, dpp_f<0x141>(v));
-  v = fmaxf(v, dpp_f<0x140>(v));
-  return v;
-}
-// v_permlane16_swap / v_permlane32_swap (CDNA4) of a value with itself: the two results hold, in
-// every lane, the lane's own row pair / half and the partner's, so their sum is the xor-16 /
-// xor-32 butterfly step without an LDS round trip (ds_bpermute).  Same operand order in every
-// lane: bitwise-identical results across the pair.
-__device__ __forceinline__ float xor16_sum(float v) {
-  const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
-}
-__device__ __forceinline__ float xor32_sum(float v) {
-  const auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
-}
-// (lower-half value, upper-half value) of v at lane (l mod 32) and (l mod 32) + 32, in every lane
-__device__ __forceinline__ void halves(float v, float& lo, float& hi) {
-  const auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  lo = __uint_as_float(q[0]);
-  hi = __uint_as_float(q[1]);
-}
-__device__ __forceinline__ float rfl(float v) {
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
-__device__ __forceinline__ float rdl(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-// LDS barrier that leaves LDS-DMA in flight (__syncthreads() would wait vmcnt(0))
-__device__ __forceinline__ void mn_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-// One LDS-DMA piece per lane (16 B from gsrc to LDS byte address m0 + 16 * lane), issued from
-// inline asm: the compiler then does not see an LDS write in flight and does not put an
-// s_waitcnt vmcnt(0) in front of every later LDS read (it cannot tell the ring slot being
-// filled from the one being read).  The kernel orders the pieces itself: counted vmcnt waits
-// (mn_wait_vm) + barrier before a slot is read, barrier before a slot is refilled.
-__device__ __forceinline__ void mn_dma16(const float* gsrc, const float* lds_dst) {
-  const uint32_t a = (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) float*)lds_dst);
-  uint32_t keep;  // m0 is compiler-reserved: save and restore it inside the statement
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(a)
-               : "memory");  // (without the clobber the compiler may move LDS reads across it)
-}
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n (stricter than asked above 31: still safe)
-__device__ __forceinline__ void mn_wait_vm(int n) {
-#define TR_VM_CASE(k) \
-  case k:             \
-    asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); \
-    break;
-  switch (n < 0 ? 0 : n) {
-    TR_VM_CASE(0) TR_VM_CASE(1) TR_VM_CASE(2) TR_VM_CASE(3) TR_VM_CASE(4) TR_VM_CASE(5) TR_VM_CASE(6)
-    TR_VM_CASE(7) TR_VM_CASE(8) TR_VM_CASE(9) TR_VM_CASE(10) TR_VM_CASE(11) TR_VM_CASE(12) TR_VM_CASE(13)
-    TR_VM_CASE(14) TR_VM_CASE(15) TR_VM_CASE(16) TR_VM_CASE(17) TR_VM_CASE(18) TR_VM_CASE(19) TR_VM_CASE(20)
-    TR_VM_CASE(21) TR_VM_CASE(22) TR_VM_CASE(23) TR_VM_CASE(24) TR_VM_CASE(25) TR_VM_CASE(26) TR_VM_CASE(27)
-    TR_VM_CASE(28) TR_VM_CASE(29) TR_VM_CASE(30) TR_VM_CASE(31)
-    default:
-      asm volatile("s_waitcnt vmcnt(31)" ::: "memory");
-  }
-#undef TR_VM_CASE
-}
 }  // namespace
 
 enum { MN_ROLE_A = 0, MN_ROLE_B = 1, MN_ROLE_IDLE = 2 };
@@ -266,7 +180,7 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
   // (the sample's base pointers are formed once per call site; FULL shapes have every piece of
   // every group valid, so no per-lane test -- and no exec-mask branch -- around the DMA)
   auto issue_at = [&](const float* src, float* dst, int gi) {
-    if (FULL || goff[gi] >= 0) mn_dma16(src + goff[gi], dst + MN_NW * gi * 256);
+    if (FULL || goff[gi] >= 0) wv_dma16<WV_NT, WV_DST_UNIFORM>(src + goff[gi], dst + MN_NW * gi * 256);
   };
   auto dma_src = [&](int64_t n) { return a.X + n * a.xld; };
   auto dma_dst = [&](int buf) { return lds + buf * SPF + wv * 256; };
@@ -280,9 +194,9 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
   __builtin_amdgcn_s_waitcnt(0);
   const int nbuf = g.nbuf;
 
-  mn_f32x4 gacc[4];  // A: gacc[0] (rows x ranks of dPhi0); B: all four (dPhi1 by row class)
+  wv_f4 gacc[4];  // A: gacc[0] (rows x ranks of dPhi0); B: all four (dPhi1 by row class)
 #pragma unroll
-  for (int q = 0; q < 4; ++q) gacc[q] = mn_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < 4; ++q) gacc[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
   float dpc = 0.f;  // A: dPhiC[c][4 rb + grow]
   double lsum = 0.0;
   const float NEG = -__builtin_huge_valf();
@@ -324,21 +238,21 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
   // dma_on: also issue this wave's LDS-DMA pieces of sample dma_n into ring slot dma_buf, one
   // piece every other k step between the MFMAs (a burst of them right after the barrier stalls
   // on the vector-memory issue queue)
-  auto gemm1 = [&](const float4(&xr)[16], int zidx, mn_f32x4(&acc)[4], float& u0, float& u1, float& u2, float& u3,
+  auto gemm1 = [&](const float4(&xr)[16], int zidx, wv_f4(&acc)[4], float& u0, float& u1, float& u2, float& u3,
                    bool dma_on, int64_t dma_n, int dma_buf) {
     const float* dsrc = dma_on ? dma_src(dma_n) : a.X;
     float* ddst = dma_dst(dma_buf);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = mn_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < 4; ++q) acc[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
     if (ROLE == MN_ROLE_A) {
 #pragma unroll
       for (int c4 = 0; c4 < 16; ++c4) {
         if (dma_on && (c4 & 1) == 0 && (c4 >> 1) < gcnt) issue_at(dsrc, ddst, c4 >> 1);
         if (FULL || 4 * c4 < klen) {
-          acc[0] = mfma_4x4(xr[c4].x, bop[4 * c4 + 0], acc[0]);
-          acc[1] = mfma_4x4(xr[c4].y, bop[4 * c4 + 1], acc[1]);
-          acc[2] = mfma_4x4(xr[c4].z, bop[4 * c4 + 2], acc[2]);
-          acc[3] = mfma_4x4(xr[c4].w, bop[4 * c4 + 3], acc[3]);
+          acc[0] = wv_mfma_4x4(xr[c4].x, bop[4 * c4 + 0], acc[0]);
+          acc[1] = wv_mfma_4x4(xr[c4].y, bop[4 * c4 + 1], acc[1]);
+          acc[2] = wv_mfma_4x4(xr[c4].z, bop[4 * c4 + 2], acc[2]);
+          acc[3] = wv_mfma_4x4(xr[c4].w, bop[4 * c4 + 3], acc[3]);
         }
       }
       acc[0] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
@@ -346,14 +260,14 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
       u = fmaf(phiU[1], acc[0].y, u);
       u = fmaf(phiU[2], acc[0].z, u);
       u = fmaf(phiU[3], acc[0].w, u);
-      u += dpp_f<0x124>(u);  // row_ror:4
-      u += dpp_f<0x128>(u);  // row_ror:8
-      u = xor16_sum(u);
-      u = xor32_sum(u);
-      u0 = rdl(u, 0);
-      u1 = rdl(u, 1);
-      u2 = rdl(u, 2);
-      u3 = rdl(u, 3);
+      u += wv_dpp<0x124>(u);  // row_ror:4
+      u += wv_dpp<0x128>(u);  // row_ror:8
+      u = wv_xor16_sum(u);
+      u = wv_xor32_sum(u);
+      u0 = wv_rdl(u, 0);
+      u1 = wv_rdl(u, 1);
+      u2 = wv_rdl(u, 2);
+      u3 = wv_rdl(u, 3);
       float zpart = wpc[0] * u0;
       zpart = fmaf(wpc[1], u1, zpart);
       zpart = fmaf(wpc[2], u2, zpart);
@@ -364,10 +278,10 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
       for (int st = 0; st < 16; ++st) {
         if (dma_on && (st & 1) == 0 && (st >> 1) < gcnt) issue_at(dsrc, ddst, st >> 1);
         if (FULL || 4 * st < klen) {
-          acc[0] = mfma_4x4(xr[st].x, bop[st], acc[0]);
-          acc[1] = mfma_4x4(xr[st].y, bop[st], acc[1]);
-          acc[2] = mfma_4x4(xr[st].z, bop[st], acc[2]);
-          acc[3] = mfma_4x4(xr[st].w, bop[st], acc[3]);
+          acc[0] = wv_mfma_4x4(xr[st].x, bop[st], acc[0]);
+          acc[1] = wv_mfma_4x4(xr[st].y, bop[st], acc[1]);
+          acc[2] = wv_mfma_4x4(xr[st].z, bop[st], acc[2]);
+          acc[3] = wv_mfma_4x4(xr[st].w, bop[st], acc[3]);
         }
       }
     }
@@ -376,16 +290,16 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
   // 0's loss term for the lanes `loss_lanes` select
   auto softmax_ce = [&](float z, int64_t y, float cw, bool loss_lanes) -> float {
     const float zz = cok ? z : NEG;
-    const float mx = row_max16(zz);
+    const float mx = wv_row_max16(zz);
     const float ez = cok ? expf(zz - mx) : 0.f;
-    const float sum = row_sum16(ez);
+    const float sum = wv_row_sum16(ez);
     const float S = ez * __builtin_amdgcn_rcpf(sum);  // softmax (model, multinomial…py:187)
-    const float m2 = row_max16(cok ? S : NEG);
+    const float m2 = wv_row_max16(cok ? S : NEG);
     const float q = cok ? expf(S - m2) : 0.f;
-    const float s2 = row_sum16(q);
+    const float s2 = wv_row_sum16(q);
     const bool is_y = cok && (int64_t)c == y;
     const float dS = cok ? (q * __builtin_amdgcn_rcpf(s2) - (is_y ? 1.0f : 0.0f)) * (cw * a.scale) : 0.f;
-    const float dot = row_sum16(dS * S);
+    const float dot = wv_row_sum16(dS * S);
     if (ROLE == MN_ROLE_A) {
       const float ce = -((S - m2) - logf(s2));  // CrossEntropyLoss on the probabilities
       lsum += (wv == 0 && is_y && loss_lanes) ? (double)cw * (double)ce : 0.0;
@@ -403,20 +317,20 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
 #pragma unroll
       for (int gi = 0; gi < kMnlGMax; ++gi)
         if (gi < gcnt) issue_group(sample_of(k), (int)k, gi);
-    mn_f32x4 accP[4], accC[4];
+    wv_f4 accP[4], accC[4];
     float uP0 = 0.f, uP1 = 0.f, uP2 = 0.f, uP3 = 0.f, uC0 = 0.f, uC1 = 0.f, uC2 = 0.f, uC3 = 0.f;
     int64_t yP = 0, yC = 0;
     float cwP = 0.f, cwC = 0.f;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) accP[q] = accC[q] = mn_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < 4; ++q) accP[q] = accC[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
     for (int64_t k = 0; k <= nr; ++k) {
       if (k < nr) {
         int64_t ahead = nr - 1 - k;
         if (ahead > nbuf - 2) ahead = nbuf - 2;
-        mn_wait_vm(gcnt * (int)ahead);  // sample k has landed (this wave's pieces)
+        wv_wait_vm<31>(gcnt * (int)ahead);  // sample k has landed (this wave's pieces)
       }
       TR_MNL_MARK(0);
-      mn_barrier();  // every wave's pieces of sample k; Z partials of k - 1; slot (k - 1) % nbuf free
+      wv_barrier();  // every wave's pieces of sample k; Z partials of k - 1; slot (k - 1) % nbuf free
       TR_MNL_MARK(1);
       const bool pre = k + nbuf - 1 < nr;  // refill slot (k - 1) % nbuf with sample k + nbuf - 1
       const int64_t npre = pre ? sample_of(k + nbuf - 1) : 0;
@@ -434,8 +348,8 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
           const float4 zp = *reinterpret_cast<const float4*>(sZ + (zs * 16 + c) * 4);
           const float dz = softmax_ce(((zp.x + zp.y) + zp.z) + zp.w, yP, cwP, lane < 16);
           // Wv[4 rb + g] = sum_c dZ[c] w PhiC[c][4 rb + g] in DPP row g; lane rank 4 rb + (l & 3)
-          const float wrow = row_sum16(dz * pcg);
-          const float w0 = rdl(wrow, 0), w1 = rdl(wrow, 16), w2 = rdl(wrow, 32), w3 = rdl(wrow, 48);
+          const float wrow = wv_row_sum16(dz * pcg);
+          const float w0 = wv_rdl(wrow, 0), w1 = wv_rdl(wrow, 16), w2 = wv_rdl(wrow, 32), w3 = wv_rdl(wrow, 48);
           const float wvl = l3 == 0 ? w0 : l3 == 1 ? w1 : l3 == 2 ? w2 : w3;
           if (ROLE == MN_ROLE_A) {
             gacc[0] += wvl * accP[0];
@@ -448,7 +362,7 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
         }
         if (k < nr) {
           yC = lab[sample_of(k)];
-          cwC = rdl(cwl, (int)yC);
+          cwC = wv_rdl(cwl, (int)yC);
           float4 xr[16];
           load1((int)(k % nbuf), xr);
           gemm1(xr, (int)(k & 1), accC, uC0, uC1, uC2, uC3, pre, npre, bpre);
@@ -483,9 +397,9 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
     };
     for (int p = 0; p < nps - 1 && p < np; ++p) issue_pair(p, p);
     int slot_cur = 0, slot_pre = nps - 1;  // ring slots of pair p and of pair p + nps - 1 (mod nps)
-    mn_f32x4 accA[4], accB[4];  // members a, b of the previous pair (GEMM output of this pair)
+    wv_f4 accA[4], accB[4];  // members a, b of the previous pair (GEMM output of this pair)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) accA[q] = accB[q] = mn_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < 4; ++q) accA[q] = accB[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
     float ua0 = 0.f, ua1 = 0.f, ua2 = 0.f, ua3 = 0.f, ub0 = 0.f, ub1 = 0.f, ub2 = 0.f, ub3 = 0.f;
     int64_t ya = 0, yb = 0;
     float cwa = 0.f, cwb = 0.f;
@@ -494,10 +408,10 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
       if (p < np) {
         int ahead = np - 1 - p;
         if (ahead > nps - 2) ahead = nps - 2;
-        mn_wait_vm(2 * gcnt * ahead);  // pair p has landed (this wave's pieces)
+        wv_wait_vm<31>(2 * gcnt * ahead);  // pair p has landed (this wave's pieces)
       }
       TR_MNL_MARK(0);
-      mn_barrier();  // every wave's pieces of pair p; Z partials of p - 1; slots of pair p - 1 free
+      wv_barrier();  // every wave's pieces of pair p; Z partials of p - 1; slots of pair p - 1 free
       TR_MNL_MARK(1);
       const bool pre = p + nps - 1 < np;  // refill the slots of pair p - 1 with pair p + nps - 1
       const bool pre_in_gemm = ROLE != MN_ROLE_IDLE && p < np;
@@ -515,15 +429,15 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
           const int64_t yh = h ? yb : ya;
           const float cwh = h ? cwb : cwa;
           const float dz = softmax_ce(((zp.x + zp.y) + zp.z) + zp.w, yh, cwh, (lane & 31) < 16);
-          const float s0 = row_sum16(dz * pcp0), s1 = row_sum16(dz * pcp1);
+          const float s0 = wv_row_sum16(dz * pcp0), s1 = wv_row_sum16(dz * pcp1);
           // member a: ranks q = 0, 1 in rows 0, 1 of pass 0; q = 2, 3 of pass 1; member b rows 2, 3
-          const float wa = l3 == 0 ? rdl(s0, 0) : l3 == 1 ? rdl(s0, 16) : l3 == 2 ? rdl(s1, 0) : rdl(s1, 16);
-          const float wb = l3 == 0 ? rdl(s0, 32) : l3 == 1 ? rdl(s0, 48) : l3 == 2 ? rdl(s1, 32) : rdl(s1, 48);
+          const float wa = l3 == 0 ? wv_rdl(s0, 0) : l3 == 1 ? wv_rdl(s0, 16) : l3 == 2 ? wv_rdl(s1, 0) : wv_rdl(s1, 16);
+          const float wb = l3 == 0 ? wv_rdl(s0, 32) : l3 == 1 ? wv_rdl(s0, 48) : l3 == 2 ? wv_rdl(s1, 32) : wv_rdl(s1, 48);
           if (ROLE == MN_ROLE_A) {
             gacc[0] += wa * accA[0];
             gacc[0] += wb * accB[0];
             float dza, dzb;  // both members' dZ[c] in every lane
-            halves(dz, dza, dzb);
+            wv_halves(dz, dza, dzb);
             const float uga = grow == 0 ? ua0 : grow == 1 ? ua1 : grow == 2 ? ua2 : ua3;
             const float ugb = grow == 0 ? ub0 : grow == 1 ? ub1 : grow == 2 ? ub2 : ub3;
             dpc = fmaf(dza, wg * uga, dpc);
@@ -540,9 +454,9 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
         if (p < np) {
           const int s0 = 2 * slot_cur, zs = p & 1;
           ya = lab[member_sample(2 * p)];
-          cwa = rdl(cwl, (int)ya);
+          cwa = wv_rdl(cwl, (int)ya);
           yb = lab[member_sample(2 * p + 1)];
-          cwb = 2 * p + 1 < nr ? rdl(cwl, (int)yb) : 0.f;
+          cwb = 2 * p + 1 < nr ? wv_rdl(cwl, (int)yb) : 0.f;
           load1(s0, xra, HO, 16);
           gemm1(xra, zs * 2, accA, ua0, ua1, ua2, ua3, pre, pre ? member_sample(2 * pq) : 0, spre);
           TR_MNL_MARK(5);
@@ -602,7 +516,7 @@ __device__ __forceinline__ void mnl_body(const MnlGeom& g, const MnArgs& a, cons
     __syncthreads();
   }
   if (ROLE == MN_ROLE_A && wv == 0) {
-    lsum = tr_wave_allreduce_d(lsum);
+    lsum = wv_allreduce_d(lsum);
     if (lane == 0) {
       a.dpart[2 * blockIdx.x] = lsum;
       a.dpart[2 * blockIdx.x + 1] = 0.0;

@@ -47,6 +47,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "tr_bf16_split.h"
 #include "tr_common.h"
 #include "tr_mnl.h"
 
@@ -89,92 +90,29 @@ constexpr int DU_T = DU_NW * TR_WAVE;
 //    epilogue stages stay between the steps;
 //  - the non-temporal policy on the sample pieces (rank-block 0.364 -> 0.339 ms at c3).
 constexpr int XL = 6, XLA = 4;
-typedef float du_f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ du_f32x4 du_mfma(float a, float b, du_f32x4 c) {
+// the MFMAs of both bodies, behind the TR_DUO_SKIP & 2 ablation
+__device__ __forceinline__ wv_f4 du_mfma(float a, float b, wv_f4 c) {
   if (TR_DUO_SKIP & 2) return c + a * b;  // one VALU op instead of the MFMA (keeps the operand reads)
-  return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0);
-}
-template <int CTRL>
-__device__ __forceinline__ float du_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float du_row_sum16(float v) {
-  v += du_dpp<0xB1>(v);
-  v += du_dpp<0x4E>(v);
-  v += du_dpp<0x141>(v);
-  v += du_dpp<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ float du_row_max16(float v) {
-  v = fmaxf(v, du_dpp<0xB1>(v));
-  v = fmaxf(v, du_dpp<0x4E>(v));
-  v = fmaxf(v, du_dpp<0x141>(v));
-  v = fmaxf(v, du_dpp<0x140>(v));
-  return v;
-}
-__device__ __forceinline__ float du_xor16_sum(float v) {
-  const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
-}
-__device__ __forceinline__ float du_xor32_sum(float v) {
-  const auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
+  return wv_mfma_4x4(a, b, c);
 }
 // exp / log on the hardware base-2 units (v_exp_f32 / v_log_f32, ~1 ulp): the epilogue's
 // arguments are bounded (exp of values <= 0 and of S in [0, 1], log of a sum in [1, 16 e])
 __device__ __forceinline__ float du_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 __device__ __forceinline__ float du_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-__device__ __forceinline__ float du_rdl(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ void du_barrier() {  // leaves LDS-DMA in flight
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void du_dma16(const float* gsrc, const float* lds_dst) {
-  const uint32_t a = (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) float*)lds_dst);
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(a))
-               : "memory");
-}
-// ---- bf16 split helpers (the bsp form below; same pieces as tr_spectral_slice.hip) ----
-typedef __bf16 bs_bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bs_bf2 __attribute__((ext_vector_type(2)));
-typedef uint32_t sl_u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ du_f32x4 bs_mfma(sl_u4 a, const uint32_t (&b)[4], du_f32x4 c) {
+// the split body's MFMAs (bf16 pieces from tr_bf16_split.h; the f16 form of the second X piece)
+__device__ __forceinline__ wv_f4 bs_mfma(wv_u4 a, const uint32_t (&b)[4], wv_f4 c) {
   if (TR_DUO_SKIP & 2) return c + __uint_as_float(a[0]) * __uint_as_float(b[0]);
-  const sl_u4 bb = sl_u4{b[0], b[1], b[2], b[3]};
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bs_bf8, a), __builtin_bit_cast(bs_bf8, bb), c, 0,
-                                                 0, 0);
+  return wv_mfma_bf16(a, wv_u4{b[0], b[1], b[2], b[3]}, c);
 }
-// two values -> one VGPR of packed round-to-nearest-even bf16 (element 0 = a), v_cvt_pk_bf16_f32
-__device__ __forceinline__ uint32_t sl_pack_rne(float a, float b) {
-  return __builtin_bit_cast(uint32_t, bs_bf2{(__bf16)a, (__bf16)b});
+__device__ __forceinline__ wv_f4 bs_mfma_h(wv_u4 a, const uint32_t (&b)[4], wv_f4 c) {
+  if (TR_DUO_SKIP & 2) return c + __uint_as_float(a[0]) * __uint_as_float(b[0]);
+  return wv_mfma_f16(a, wv_u4{b[0], b[1], b[2], b[3]}, c);
 }
-typedef _Float16 bs_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 bs_h2 __attribute__((ext_vector_type(2)));
 // two values -> one VGPR of packed round-to-nearest-even f16, v_cvt_pk_f16_f32
+typedef _Float16 bs_h2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t bs_pack_h(float a, float b) {
   return __builtin_bit_cast(uint32_t, bs_h2{(_Float16)a, (_Float16)b});
-}
-__device__ __forceinline__ du_f32x4 bs_mfma_h(sl_u4 a, const uint32_t (&b)[4], du_f32x4 c) {
-  if (TR_DUO_SKIP & 2) return c + __uint_as_float(a[0]) * __uint_as_float(b[0]);
-  const sl_u4 bb = sl_u4{b[0], b[1], b[2], b[3]};
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(bs_h8, a), __builtin_bit_cast(bs_h8, bb), c, 0, 0,
-                                                0);
-}
-__device__ __forceinline__ float sl_lo_f32(uint32_t h) { return __uint_as_float(__builtin_amdgcn_perm(h, h, 0x01000c0cu)); }
-__device__ __forceinline__ float sl_hi_f32(uint32_t h) { return __uint_as_float(h & 0xffff0000u); }
-// a (element 2m), b (element 2m + 1) -> three packed round-to-nearest pieces: x = x1 + x2 + x3 exactly
-__device__ __forceinline__ void sl_split2(float a, float b, uint32_t& h1, uint32_t& h2, uint32_t& h3) {
-  h1 = sl_pack_rne(a, b);
-  const float ra = a - sl_lo_f32(h1), rb = b - sl_hi_f32(h1);
-  h2 = sl_pack_rne(ra, rb);
-  h3 = sl_pack_rne(ra - sl_lo_f32(h2), rb - sl_hi_f32(h2));
 }
 }  // namespace
 
@@ -296,17 +234,17 @@ __device__ __forceinline__ void duo_body(const MnlGeom& g, const DuArgs& a, cons
     __builtin_amdgcn_s_waitcnt(0);
   }
 
-  du_f32x4 gT = du_f32x4{0.f, 0.f, 0.f, 0.f};  // dPhi0 rows x ranks of the T unit
-  du_f32x4 gV[4];                                // dPhi1 of the V unit, by row class
+  wv_f4 gT = wv_f4{0.f, 0.f, 0.f, 0.f};  // dPhi0 rows x ranks of the T unit
+  wv_f4 gV[4];                                // dPhi1 of the V unit, by row class
 #pragma unroll
-  for (int q = 0; q < 4; ++q) gV[q] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < 4; ++q) gV[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
   float dpc = 0.f;  // dPhiC[c][4 rb + row] of the T unit
   double lsum = 0.0;
 
-  du_f32x4 TP = du_f32x4{0.f, 0.f, 0.f, 0.f};  // previous sample's T (summed) and V (by row class)
-  du_f32x4 VP[4];
+  wv_f4 TP = wv_f4{0.f, 0.f, 0.f, 0.f};  // previous sample's T (summed) and V (by row class)
+  wv_f4 VP[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) VP[q] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < 4; ++q) VP[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
   float uP[4] = {0.f, 0.f, 0.f, 0.f};
   int64_t yP = 0;  // label / class weight of the sample in the epilogue
   float cwP = 0.f;
@@ -332,10 +270,10 @@ __device__ __forceinline__ void duo_body(const MnlGeom& g, const DuArgs& a, cons
       e_zp = *reinterpret_cast<const float4*>(sZ + (zs * 16 + c) * 4);
     } else if (st == 1) {
       const float zz = cok ? ((e_zp.x + e_zp.y) + e_zp.z) + e_zp.w : NEG;
-      e_x = zz - du_row_max16(zz);
+      e_x = zz - wv_row_max16(zz);
     } else if (st == 2) {
       e_ez = cok ? du_exp(e_x) : 0.f;
-      e_sum = du_row_sum16(e_ez);
+      e_sum = wv_row_sum16(e_ez);
     } else if (st == 3) {
       e_S = e_ez * __builtin_amdgcn_rcpf(e_sum);
       e_q = cok ? du_exp(e_S) : 0.f;
@@ -343,12 +281,12 @@ __device__ __forceinline__ void duo_body(const MnlGeom& g, const DuArgs& a, cons
       e_Sq = e_S * e_q;
       e_Sy = e_isy ? e_S : 0.f;
     } else if (st == 4) {
-      e_s2 = du_row_sum16(e_q);
-      e_d1 = du_row_sum16(e_Sq);
-      e_e1 = du_row_sum16(e_Sy);
-      e_ar = du_row_sum16(e_Sq * pcg);
-      e_br = du_row_sum16(e_S * pcg);
-      e_yr = du_row_sum16(e_Sy * pcg);
+      e_s2 = wv_row_sum16(e_q);
+      e_d1 = wv_row_sum16(e_Sq);
+      e_e1 = wv_row_sum16(e_Sy);
+      e_ar = wv_row_sum16(e_Sq * pcg);
+      e_br = wv_row_sum16(e_S * pcg);
+      e_yr = wv_row_sum16(e_Sy * pcg);
     } else if (st == 5) {
       const float is2 = __builtin_amdgcn_rcpf(e_s2);
       const float kk = cwE * a.scale;
@@ -359,7 +297,7 @@ __device__ __forceinline__ void duo_body(const MnlGeom& g, const DuArgs& a, cons
       e_wr = kk * (e_ar * is2 - e_yr) - dot * e_br;
     } else if (st == 6) {
       // Wv[4 rb + g] in DPP row g -> lane rank 4 rb + (l & 3) by 0/1 lane masks (no branches)
-      const float w0 = du_rdl(e_wr, 0), w1 = du_rdl(e_wr, 16), w2 = du_rdl(e_wr, 32), w3 = du_rdl(e_wr, 48);
+      const float w0 = wv_rdl(e_wr, 0), w1 = wv_rdl(e_wr, 16), w2 = wv_rdl(e_wr, 32), w3 = wv_rdl(e_wr, 48);
       e_wv = fmaf(w3, sel[3], fmaf(w2, sel[2], fmaf(w1, sel[1], w0 * sel[0])));
     } else {
       gT += e_wv * TP;
@@ -397,16 +335,16 @@ __device__ __forceinline__ void duo_body(const MnlGeom& g, const DuArgs& a, cons
     yN = lab[sample_of(more ? k + 1 : k)];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     TR_DUO_MARK(0);
-    du_barrier();  // everyone's pieces of k; Z partials of k - 1; slot SL ^ 1 free
+    wv_barrier();  // everyone's pieces of k; Z partials of k - 1; slot SL ^ 1 free
     TR_DUO_MARK(1);
-    const float cwC = du_rdl(cwl, (int)yC);
+    const float cwC = wv_rdl(cwl, (int)yC);
     const float* psrc = (more && !(TR_DUO_SKIP & 1)) ? src_of(k + 1) : src_of(k);
     const uint32_t pm0 = lbase + (uint32_t)((SL ^ 1) * 4 * SPF) + (uint32_t)wv * 1024u;
     epi(0, SL ^ 1, yP, cwP);
     const float* sb = lds + SL * SPF;
-    du_f32x4 aT[4], aV[4];
+    wv_f4 aT[4], aV[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) aT[q] = aV[q] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < 4; ++q) aT[q] = aV[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
     // operand quads read ahead of their MFMAs (bounded live registers)
     float4 xt[16], bq[16], xv[16];
     auto ldT = [&](int st) {
@@ -442,7 +380,7 @@ __device__ __forceinline__ void duo_body(const MnlGeom& g, const DuArgs& a, cons
     }
     TR_DUO_MARK(2);
     // T of sample k -> U partial of this unit -> Z partial (16 classes) -> LDS
-    const du_f32x4 T = (aT[0] + aT[1]) + (aT[2] + aT[3]);
+    const wv_f4 T = (aT[0] + aT[1]) + (aT[2] + aT[3]);
     TP = T;
 #pragma unroll
     for (int q = 0; q < 4; ++q) VP[q] = aV[q];
@@ -450,14 +388,14 @@ __device__ __forceinline__ void duo_body(const MnlGeom& g, const DuArgs& a, cons
     u = fmaf(phiU[1], T.y, u);
     u = fmaf(phiU[2], T.z, u);
     u = fmaf(phiU[3], T.w, u);
-    u += du_dpp<0x124>(u);  // row_ror:4
-    u += du_dpp<0x128>(u);  // row_ror:8
-    u = du_xor16_sum(u);
-    u = du_xor32_sum(u);
-    uP[0] = du_rdl(u, 0);
-    uP[1] = du_rdl(u, 1);
-    uP[2] = du_rdl(u, 2);
-    uP[3] = du_rdl(u, 3);
+    u += wv_dpp<0x124>(u);  // row_ror:4
+    u += wv_dpp<0x128>(u);  // row_ror:8
+    u = wv_xor16_sum(u);
+    u = wv_xor32_sum(u);
+    uP[0] = wv_rdl(u, 0);
+    uP[1] = wv_rdl(u, 1);
+    uP[2] = wv_rdl(u, 2);
+    uP[3] = wv_rdl(u, 3);
     float zpart = wpc[0] * uP[0];
     zpart = fmaf(wpc[1], uP[1], zpart);
     zpart = fmaf(wpc[2], uP[2], zpart);
@@ -477,7 +415,7 @@ __device__ __forceinline__ void duo_body(const MnlGeom& g, const DuArgs& a, cons
     for (int q = 0; q < 4; ++q) g_duo_prof[blockIdx.x][wv][q] = prof[q];
 #endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last (harmless) refill has landed
-  du_barrier();  // Z partials of the last sample
+  wv_barrier();  // Z partials of the last sample
   if (nr > 0) {
 #pragma unroll
     for (int st = 0; st < 8; ++st) epi(st, (nr - 1) & 1, yP, cwP);
@@ -518,7 +456,7 @@ __device__ __forceinline__ void duo_body(const MnlGeom& g, const DuArgs& a, cons
     __syncthreads();
   }
   if (wv == 0) {
-    lsum = tr_wave_allreduce_d(lsum);
+    lsum = wv_allreduce_d(lsum);
     if (lane == 0) {
       a.dpart[2 * blockIdx.x] = lsum;
       a.dpart[2 * blockIdx.x + 1] = 0.0;
@@ -645,7 +583,7 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
   uint32_t bT12[NKT][4], bT2[N2][4], bT3[NKT][4], hT[NKT][4], bV12[4], bV2[4], bV3[4], hV[4];
   auto bsplit = [&](float x0, float x1, uint32_t& b12, uint32_t& b2, uint32_t& b3, uint32_t& hh) {
     uint32_t h1, h2, h3;
-    sl_split2(x0, x1, h1, h2, h3);
+    bfs_split2(x0, x1, h1, h2, h3);
     if constexpr (R16) {
       b12 = h1;
       b2 = h2;
@@ -791,21 +729,21 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
   __syncthreads();
   __builtin_amdgcn_s_waitcnt(0);
 
-  du_f32x4 gT[NT], gV[NVS];  // dPhi0 rows of this wave's T tiles, dPhi1 partial of its V tiles
+  wv_f4 gT[NT], gV[NVS];  // dPhi0 rows of this wave's T tiles, dPhi1 partial of its V tiles
 #pragma unroll
-  for (int q = 0; q < NT; ++q) gT[q] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < NT; ++q) gT[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int q = 0; q < NVS; ++q) gV[q] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < NVS; ++q) gV[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
   float dpc[KR];  // wave 0: dPhiC[c][gq + 4 k]
 #pragma unroll
   for (int k = 0; k < KR; ++k) dpc[k] = 0.f;
   double lsum = 0.0;
-  du_f32x4 TP[NT], VP[NVS];  // the previous sample's T and V (folded), for its epilogue
-  du_f32x4 TN[NT], VN[NVS];  // DIST: this sample's, from the fold to the next iteration's top
+  wv_f4 TP[NT], VP[NVS];  // the previous sample's T and V (folded), for its epilogue
+  wv_f4 TN[NT], VN[NVS];  // DIST: this sample's, from the fold to the next iteration's top
 #pragma unroll
-  for (int q = 0; q < NT; ++q) TP[q] = TN[q] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < NT; ++q) TP[q] = TN[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int q = 0; q < NVS; ++q) VP[q] = VN[q] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < NVS; ++q) VP[q] = VN[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
   // DIST: Wv of the sample in ring slot zs (published by its owner) onto the held T, V; then the
   // newest sample's T, V are the held ones
   auto dist_apply = [&](int zs) {
@@ -841,12 +779,12 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
       for (int w = 1; w < NW; ++w) E.uS += pu[RK * w];
     } else if (st == 1) {
 #pragma unroll
-      for (int r = 0; r < RK; ++r) E.uR[r] = du_rdl(E.uS, r);
+      for (int r = 0; r < RK; ++r) E.uR[r] = wv_rdl(E.uS, r);
       float zz;
       if constexpr (PCL) {
-        du_f32x4 pq[RK / 4];
+        wv_f4 pq[RK / 4];
 #pragma unroll
-        for (int h = 0; h < RK / 4; ++h) pq[h] = *reinterpret_cast<const du_f32x4*>(sPC + RK * c + 4 * h);
+        for (int h = 0; h < RK / 4; ++h) pq[h] = *reinterpret_cast<const wv_f4*>(sPC + RK * c + 4 * h);
         zz = pq[0][0] * E.uR[0];
 #pragma unroll
         for (int r = 1; r < RK; ++r) zz = fmaf(pq[r / 4][r % 4], E.uR[r], zz);
@@ -856,10 +794,10 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
         for (int r = 1; r < 8; ++r) zz = fmaf(pc[r], E.uR[r], zz);
       }
       zz = cok ? zz : NEG;
-      E.e_x = zz - du_row_max16(zz);
+      E.e_x = zz - wv_row_max16(zz);
     } else if (st == 2) {
       E.e_ez = cok ? du_exp(E.e_x) : 0.f;
-      E.e_sum = du_row_sum16(E.e_ez);
+      E.e_sum = wv_row_sum16(E.e_ez);
     } else if (st == 3) {
       E.e_S = E.e_ez * __builtin_amdgcn_rcpf(E.e_sum);
       E.e_q = cok ? du_exp(E.e_S) : 0.f;
@@ -867,15 +805,15 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
       E.e_Sq = E.e_S * E.e_q;
       E.e_Sy = E.e_isy ? E.e_S : 0.f;
     } else if (st == 4) {
-      E.e_s2 = du_row_sum16(E.e_q);
-      E.e_d1 = du_row_sum16(E.e_Sq);
-      E.e_e1 = du_row_sum16(E.e_Sy);
+      E.e_s2 = wv_row_sum16(E.e_q);
+      E.e_d1 = wv_row_sum16(E.e_Sq);
+      E.e_e1 = wv_row_sum16(E.e_Sy);
 #pragma unroll
       for (int k = 0; k < KR; ++k) {
         const float pk = pcg_of(k);
-        E.e_a[k] = du_row_sum16(E.e_Sq * pk);
-        E.e_b[k] = du_row_sum16(E.e_S * pk);
-        E.e_y[k] = du_row_sum16(E.e_Sy * pk);
+        E.e_a[k] = wv_row_sum16(E.e_Sq * pk);
+        E.e_b[k] = wv_row_sum16(E.e_S * pk);
+        E.e_y[k] = wv_row_sum16(E.e_Sy * pk);
       }
     } else if (st == 5) {
       const float is2 = __builtin_amdgcn_rcpf(E.e_s2);
@@ -912,8 +850,8 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
           for (int bb = 0; bb < nb - 1; ++bb)
 #pragma unroll
             for (int tt = 0; tt < NT; ++tt) {
-              const du_f32x4 tp = *reinterpret_cast<const du_f32x4*>(sTB + tb_at(bb, tt));
-              du_f32x4* gp = reinterpret_cast<du_f32x4*>(sTB + tbn + tb_at(bb, tt));
+              const wv_f4 tp = *reinterpret_cast<const wv_f4*>(sTB + tb_at(bb, tt));
+              wv_f4* gp = reinterpret_cast<wv_f4*>(sTB + tbn + tb_at(bb, tt));
               *gp += E.e_wv * tp;
             }
       }
@@ -926,8 +864,8 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
           // owner's chain; selecting among E.uR[] elements would put E in scratch)
           float uk;
           if constexpr (DIST) {
-            const float u0 = du_rdl(E.uS, 4 * k), u1 = du_rdl(E.uS, 4 * k + 1), u2 = du_rdl(E.uS, 4 * k + 2),
-                        u3 = du_rdl(E.uS, 4 * k + 3);
+            const float u0 = wv_rdl(E.uS, 4 * k), u1 = wv_rdl(E.uS, 4 * k + 1), u2 = wv_rdl(E.uS, 4 * k + 2),
+                        u3 = wv_rdl(E.uS, 4 * k + 3);
             uk = gq < 2 ? (gq == 0 ? u0 : u1) : (gq == 2 ? u2 : u3);
           } else {
             uk = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * gq + 16 * k, __float_as_int(E.uS)));
@@ -989,15 +927,15 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
     else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     TR_DUO_MARK(0);
-    du_barrier();  // everyone's pieces of k; U partials of k - 1
+    wv_barrier();  // everyone's pieces of k; U partials of k - 1
     TR_DUO_MARK(1);
     float cwC;
     if constexpr (BLK) {
-      if (bfirst) cwB = du_rdl(cwl, (int)yC);
+      if (bfirst) cwB = wv_rdl(cwl, (int)yC);
       cwC = cwB;
       split_rows();  // this block's Phi0 operands (loaded at the end of the previous block)
     } else {
-      cwC = du_rdl(cwl, (int)yC);
+      cwC = wv_rdl(cwl, (int)yC);
     }
     if constexpr (DIST) dist_apply((SL + 2 * NS - 2) % NS);  // Wv(k - 2), published at the end of k - 1
     // sample k + 2 into this slot once it is read (past the end: a harmless refill of a valid sample)
@@ -1018,44 +956,44 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
     const bool own = !DIST || (k + NW - 1) % NW == wv;
     if (bfirst && own) epi(E, 0, zsP, yP, cwP);
     const float* sb = lds + SL * SPF;
-    du_f32x4 aT[NT], aV[NVS];
+    wv_f4 aT[NT], aV[NVS];
 #pragma unroll
-    for (int q = 0; q < NT; ++q) aT[q] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < NT; ++q) aT[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int q = 0; q < NVS; ++q) aV[q] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < NVS; ++q) aV[q] = wv_f4{0.f, 0.f, 0.f, 0.f};
     // every operand of sample k into registers
     constexpr int NU = NT * NKT;  // T steps (4; J = 32: 2); then NVS V steps (one j-tile each)
-    du_f32x4 xv[8], xt[NU][2];
+    wv_f4 xv[8], xt[NU][2];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) xv[e] = *reinterpret_cast<const du_f32x4*>(sb + vro[e]);
+    for (int e = 0; e < 8; ++e) xv[e] = *reinterpret_cast<const wv_f4*>(sb + vro[e]);
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
       const int tt = u / NKT, s = u - tt * NKT;
       const int q0 = 8 * s + 2 * gq;
-      xt[u][0] = *reinterpret_cast<const du_f32x4*>(sb + tro[tt] + 4 * (q0 ^ tsw));
-      xt[u][1] = *reinterpret_cast<const du_f32x4*>(sb + tro[tt] + 4 * ((q0 + 1) ^ tsw));
+      xt[u][0] = *reinterpret_cast<const wv_f4*>(sb + tro[tt] + 4 * (q0 ^ tsw));
+      xt[u][1] = *reinterpret_cast<const wv_f4*>(sb + tro[tt] + 4 * ((q0 + 1) ^ tsw));
     }
 #pragma unroll
     for (int st = 0; st < NU + NVS; ++st) {
       if (!(TR_DUO_SKIP & 8)) dma_piece(goff_of(st), src_of_group(psrc, st), pm0 + (uint32_t)st * (uint32_t)(NW * 1024));
-      sl_u4 x1, x2, x3;  // the k step's X pieces (pairs per VGPR)
+      wv_u4 x1, x2, x3;  // the k step's X pieces (pairs per VGPR)
       auto split = [&](float e0, float e1, int v) {
         if constexpr (EXACT) {
           uint32_t h1, h2, h3;
-          sl_split2(e0, e1, h1, h2, h3);
+          bfs_split2(e0, e1, h1, h2, h3);
           x1[v] = h1;
           x2[v] = h2;
           x3[v] = h3;
         } else {
-          const uint32_t h = sl_pack_rne(e0, e1);
+          const uint32_t h = bfs_pack_rne(e0, e1);
           x1[v] = h;
-          x2[v] = bs_pack_h(e0 - sl_lo_f32(h), e1 - sl_hi_f32(h));
+          x2[v] = bs_pack_h(e0 - bfs_lo_f32(h), e1 - bfs_hi_f32(h));
         }
       };
       // smallest products first into the accumulator
       // (RK = 16: acc += x3 b1 + x2 b2 + x2 b1 + x1 b3 + x1 b2 + x1 b1 exact, x2 h + x1 b3 + x1 b2 +
       // x1 b1 fast; dropped x3 b2, x2 b3, x3 b3: < 2^-25 |x b|)
-      auto gemm = [&](du_f32x4& acc, const uint32_t (&b12)[4], const uint32_t (&b2)[4], const uint32_t (&b3)[4],
+      auto gemm = [&](wv_f4& acc, const uint32_t (&b12)[4], const uint32_t (&b2)[4], const uint32_t (&b3)[4],
                       const uint32_t (&hh)[4]) {
         if constexpr (R16) {
           if constexpr (EXACT) {
@@ -1082,7 +1020,7 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
       if (st < NU) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-          const du_f32x4& xr = xt[st][v >> 1];
+          const wv_f4& xr = xt[st][v >> 1];
           split(xr[2 * (v & 1)], xr[2 * (v & 1) + 1], v);
         }
         const int tt = st / NKT, s = st - tt * NKT;
@@ -1119,7 +1057,7 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
     for (int tt = 0; tt < NT; ++tt) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        if constexpr (!R16) aT[tt][v] += du_dpp<0x128>(aT[tt][v]);  // row_ror:8
+        if constexpr (!R16) aT[tt][v] += wv_dpp<0x128>(aT[tt][v]);  // row_ror:8
         u = fmaf(phiU[tt][v], aT[tt][v], u);
       }
       if (blast && DIST) {
@@ -1127,7 +1065,7 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
       } else if (blast) {
         TP[tt] = aT[tt];
       } else if (lo8) {  // (BLK) block b's T until the sample's epilogue
-        *reinterpret_cast<du_f32x4*>(sTB + tb_at(b, tt)) = aT[tt];
+        *reinterpret_cast<wv_f4*>(sTB + tb_at(b, tt)) = aT[tt];
       }
     }
     if constexpr (BLK) {
@@ -1148,13 +1086,13 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
       for (int q = 0; q < NVS; ++q) {
 #pragma unroll
         for (int v = 0; v < 4; ++v)
-          if constexpr (!R16) aV[q][v] += du_dpp<0x128>(aV[q][v]);
+          if constexpr (!R16) aV[q][v] += wv_dpp<0x128>(aV[q][v]);
         if constexpr (DIST)
           VN[q] = aV[q];
         else
           VP[q] = aV[q];
       }
-      u = du_xor32_sum(du_xor16_sum(u));  // lane (n < RK, any row): this wave's U partial of rank n
+      u = wv_xor32_sum(wv_xor16_sum(u));  // lane (n < RK, any row): this wave's U partial of rank n
       if (lane < RK) sU[zsC * (RK * NW) + wv * RK + lane] = u;
       yP = yC;
       cwP = cwC;
@@ -1186,7 +1124,7 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
     for (int q = 0; q < 4; ++q) g_duo_prof[blockIdx.x][wv][q] = prof[q];
 #endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last (harmless) refill has landed
-  du_barrier();  // U partials of the last sample
+  wv_barrier();  // U partials of the last sample
   if (DIST && nr > 0) {  // Wv(nr - 2) onto its T, V; the last sample's epilogue on its owner; its Wv
     dist_apply((nr + NS - 2) % NS);
     if ((nr - 1) % NW == wv) {
@@ -1194,7 +1132,7 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
 #pragma unroll
       for (int st = 0; st < 8; ++st) epi(E, st, (nr - 1) % NS, yP, cwP);
     }
-    du_barrier();
+    wv_barrier();
     dist_apply((nr - 1) % NS);
   } else if (nr > 0) {
     EpiSt E;
@@ -1222,7 +1160,7 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
         for (int bb = 0; bb < nb - 1; ++bb)
 #pragma unroll
           for (int tt = 0; tt < NT; ++tt) {
-            const du_f32x4 gt = *reinterpret_cast<const du_f32x4*>(sTB + tbn + tb_at(bb, tt));
+            const wv_f4 gt = *reinterpret_cast<const wv_f4*>(sTB + tbn + tb_at(bb, tt));
 #pragma unroll
             for (int v = 0; v < 4; ++v) sG[(bb * I + it0 + 16 * tt + 4 * gq + v) * R + r8] += gt[v];
           }
@@ -1249,7 +1187,7 @@ __device__ __forceinline__ void bsp_body(const MnlGeom& g, const DuArgs& a, cons
       for (int w = 0; w < NW; ++w) s += sLs[w];
       lsum = s;
     } else {
-      lsum = tr_wave_allreduce_d(lsum);
+      lsum = wv_allreduce_d(lsum);
     }
     if (lane == 0) {
       a.dpart[2 * blockIdx.x] = lsum;

@@ -172,7 +172,7 @@ static __device__ __forceinline__ void resident_fit(const ResArgs& a, const floa
       for (int c = 0; c < RES_MAX_C; ++c)
         if (c < C) z[c] = s[c] * (dS[c] - dot);
     }
-    lsum = tr_wave_allreduce_d(lsum);
+    lsum = wv_allreduce_d(lsum);
     if (lane == 0) dred[q] = lsum;
     __syncthreads();
     // ---- 5: G[c][p] = sum_n X[n][p] dZ[n][c], the samples in S contiguous splits ----
@@ -229,7 +229,7 @@ static __device__ __forceinline__ void resident_fit(const ResArgs& a, const floa
       const int e1 = q == 0 ? g.off1 : (q == 1 ? g.off2 : np);
       float acc = 0.f;
       for (int e = b + lane; e < e1; e += TR_WAVE) acc = fmaf(sPar[e], sPar[e], acc);
-      acc = tr_wave_allreduce(acc);
+      acc = wv_allreduce(acc);
       if (lane == 0) {
         const float nrm = sqrtf(acc);
         sNorm[q] = nrm;

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(SCORE_T) void k_mnl_score_many(const ScoreMember* _
     float mx = NEG;
 #pragma unroll
     for (int c = 0; c < SCORE_MAX_C; ++c) {
-      z[c] = c < C ? tr_wave_allreduce(z[c]) : NEG;  // (C is uniform: every lane takes part in the butterfly)
+      z[c] = c < C ? wv_allreduce(z[c]) : NEG;  // (C is uniform: every lane takes part in the butterfly)
       mx = fmaxf(mx, z[c]);
     }
     // from here every lane holds the same values

@@ -47,15 +47,9 @@ __device__ unsigned long long g_spec_prof[256][8];
 
 namespace tr {
 
-typedef float tr_f32x4_s __attribute__((ext_vector_type(4)));
-
 constexpr int kSpecNW = 8;  // waves per workgroup (two per SIMD, 256 registers each: the MFMA B
                             // fragments of one column tile + 1/512 of the next sample in flight)
 constexpr int kSpecT = kSpecNW * TR_WAVE;
-
-__device__ __forceinline__ tr_f32x4_s mfma4(float a, float b, tr_f32x4_s c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------------
 // prep: phi / dphi over the whole arena + Phi0 (W x K)
@@ -102,57 +96,6 @@ __global__ __launch_bounds__(256) void k_spec_chain(int64_t n, const float* __re
   if (stop != nullptr && *stop != 0) return;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
     grad[e] = G[e] * dphi[e];
-}
-
-// ------------------------------------------------------------------------------------------
-// LDS barrier that leaves LDS-DMA (global_load_lds) in flight: each wave retires its own LDS
-// accesses, then s_barrier.  (__syncthreads() would also wait vmcnt(0) while a glds is
-// outstanding, cdna_hip_programming.md §5 "Pipelining across barriers".)
-__device__ __forceinline__ void spec_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-// LDS-DMA pieces (16 B or 4 B per lane to LDS byte address m0 + size * lane) issued from inline
-// asm, so the compiler does not see an LDS write in flight: with the builtin it cannot tell the
-// row block being filled from the one being read and puts an `s_waitcnt vmcnt(0)` in front of the
-// GEMMs' LDS reads, draining the DMA this kernel overlaps with them.  The kernel orders the
-// pieces itself (counted spec_wait_vm + spec_barrier).  m0 is compiler-reserved: saved and
-// restored inside the statement.
-__device__ __forceinline__ uint32_t spec_lds_addr(const float* p) {
-  return (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) float*)p);
-}
-__device__ __forceinline__ void spec_dma16(const float* gsrc, const float* lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(spec_lds_addr(lds_dst)))  // wave-uniform
-               : "memory");
-}
-__device__ __forceinline__ void spec_dma4(const float* gsrc, const float* lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off nt\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(spec_lds_addr(lds_dst)))  // wave-uniform
-               : "memory");
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n (the counter is an immediate)
-__device__ __forceinline__ void spec_wait_vm(int n) {
-#define TR_VM_CASE(k) \
-  case k:             \
-    asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); \
-    break;
-  switch (n < 0 ? 0 : n) {
-    TR_VM_CASE(0) TR_VM_CASE(1) TR_VM_CASE(2) TR_VM_CASE(3) TR_VM_CASE(4) TR_VM_CASE(5) TR_VM_CASE(6)
-    TR_VM_CASE(7) TR_VM_CASE(8) TR_VM_CASE(9) TR_VM_CASE(10) TR_VM_CASE(11) TR_VM_CASE(12) TR_VM_CASE(13)
-    TR_VM_CASE(14) TR_VM_CASE(15) TR_VM_CASE(16) TR_VM_CASE(17) TR_VM_CASE(18) TR_VM_CASE(19) TR_VM_CASE(20)
-    TR_VM_CASE(21) TR_VM_CASE(22) TR_VM_CASE(23) TR_VM_CASE(24) TR_VM_CASE(25) TR_VM_CASE(26) TR_VM_CASE(27)
-    TR_VM_CASE(28) TR_VM_CASE(29) TR_VM_CASE(30) TR_VM_CASE(31)
-    default:
-      asm volatile("s_waitcnt vmcnt(31)" ::: "memory");  // stricter than asked: still safe
-  }
-#undef TR_VM_CASE
 }
 
 // ------------------------------------------------------------------------------------------
@@ -238,13 +181,13 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
   }
   // gradient tiles: w tiles 8p + grp + NGRP*u (u < KT) of block p, column tile ktw; two
   // accumulators each (even / odd k steps)
-  tr_f32x4_s gacc[NBMAX][KT][2];
+  wv_f4 gacc[NBMAX][KT][2];
 #pragma unroll
   for (int p = 0; p < NBMAX; ++p)
 #pragma unroll
     for (int u = 0; u < KT; ++u) {
-      gacc[p][u][0] = tr_f32x4_s{0.f, 0.f, 0.f, 0.f};
-      gacc[p][u][1] = tr_f32x4_s{0.f, 0.f, 0.f, 0.f};
+      gacc[p][u][0] = wv_f4{0.f, 0.f, 0.f, 0.f};
+      gacc[p][u][1] = wv_f4{0.f, 0.f, 0.f, 0.f};
     }
   float* sl = slab != nullptr ? slab + (int64_t)blockIdx.x * slab_stride : nullptr;
   // gradients of A1 / C1 in phi space, item e = j*D + d (j < Rn: A1[d, j]; else C1[d, j - Rn]),
@@ -281,13 +224,13 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
       const int64_t a = r0 >> 2, b = r1 >> 2;  // float4 range (RB*D and W*D are multiples of 4)
       for (int64_t base = a + (int64_t)wv * TR_WAVE; base < b; base += kSpecT) {
         const int64_t e4 = base + lane;
-        if (e4 < b) spec_dma16(src + 4 * e4, sX + 4 * base);
+        if (e4 < b) wv_dma16<WV_NT, WV_DST_RFL>(src + 4 * e4, sX + 4 * base);
         ++cnt;
       }
     } else {
       for (int64_t base = r0 + (int64_t)wv * TR_WAVE; base < r1; base += kSpecT) {
         const int64_t e = base + lane;
-        if (e < r1) spec_dma4(src + e, sX + base);
+        if (e < r1) wv_dma4<WV_NT, WV_DST_RFL>(src + e, sX + base);
         ++cnt;
       }
     }
@@ -314,8 +257,8 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
 #if TR_SPEC_PROFILE
     const unsigned long long w0 = __builtin_readcyclecounter();
 #endif
-    spec_wait_vm(later);
-    spec_barrier();
+    wv_wait_vm<31>(later);
+    wv_barrier();
 #if TR_SPEC_PROFILE
     prof[5] += __builtin_readcyclecounter() - w0;
 #endif
@@ -352,11 +295,11 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
       asm volatile("" : "+s"(S2));  // keep the per-step offsets inside this loop
       const bool full = set < nsets;
       const bool tail = set == 0 && g.Dtail > 0;
-      tr_f32x4_s a[TPW], at = tr_f32x4_s{0.f, 0.f, 0.f, 0.f};
+      wv_f4 a[TPW], at = wv_f4{0.f, 0.f, 0.f, 0.f};
       const float* xa[TPW];
 #pragma unroll
       for (int u = 0; u < TPW; ++u) {
-        a[u] = tr_f32x4_s{0.f, 0.f, 0.f, 0.f};
+        a[u] = wv_f4{0.f, 0.f, 0.f, 0.f};
         int dt = grp + NGRP * (set * TPW + u);
         dt = dt < g.nDF ? dt : (g.nDF > 0 ? g.nDF - 1 : 0);  // clamped duplicate: computed, not stored
         xa[u] = sX + 16 * gq * S2 + dt * 16 + i;
@@ -387,7 +330,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
 #pragma unroll
                 for (int v = 0; v < CHK; ++v)
 #pragma unroll
-                  for (int u = 0; u < TPW; ++u) a[u] = mfma4(xc[u][v], bf[c * CHK + v], a[u]);
+                  for (int u = 0; u < TPW; ++u) a[u] = wv_mfma_16x16x4(xc[u][v], bf[c * CHK + v], a[u]);
                 if (cc + 1 < CPP) {
 #pragma unroll
                   for (int v = 0; v < CHK; ++v)
@@ -399,7 +342,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
 #pragma unroll
                 for (int v = 0; v < CHK; ++v) {
                   const int s = c * CHK + v;
-                  at = mfma4(xt[(64 * (s >> 4) + (s & 15)) * S2], bf[s], at);
+                  at = wv_mfma_16x16x4(xt[(64 * (s >> 4) + (s & 15)) * S2], bf[s], at);
                 }
               }
               __builtin_amdgcn_sched_barrier(0);
@@ -423,7 +366,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
       }
     }
     if (MODE == SPEC_TRAIN && t < NO) sY[t] = ycur;
-    spec_barrier();
+    wv_barrier();
     if (MODE != SPEC_TRAIN && has_next) issue_all(sample_of(k + 1));  // X_n is no longer read
     if (g.Dtail > 0) {  // partial d tile: sum the wave groups' partials into T
       const int d16 = 16 * g.nDF;
@@ -434,7 +377,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
         for (int gg = 1; gg < NGRP; ++gg) v += sTail[(gg * g.Dtail + row) * KP + col];
         sT[(d16 + row) * KS + col] = v;
       }
-      spec_barrier();
+      wv_barrier();
     }
     TR_PROF_MARK(0);
 
@@ -495,14 +438,14 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
           }
         }
       }
-      if (TPV == 32) v += tr_swz_xor<0x401F>(v);  // xor 16
-      v += tr_swz_xor<0x201F>(v);                 // xor 8
-      v += tr_swz_xor<0x101F>(v);                 // xor 4
-      v += tr_swz_xor<0x081F>(v);                 // xor 2
-      v += tr_swz_xor<0x041F>(v);                 // xor 1
+      if (TPV == 32) v += wv_swz<0x401F>(v);  // xor 16
+      v += wv_swz<0x201F>(v);                 // xor 8
+      v += wv_swz<0x101F>(v);                 // xor 4
+      v += wv_swz<0x081F>(v);                 // xor 2
+      v += wv_swz<0x041F>(v);                 // xor 1
       if (q == 0 && j < nred) sZV[j] = v;
     }
-    spec_barrier();
+    wv_barrier();
     TR_PROF_MARK(1);
 
     if (MODE == SPEC_LATENT) {
@@ -548,16 +491,16 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
         }
         float pl = r < Rn ? c * zr : 0.f;
         float ps = r < Rn ? 0.f : c * zr;
-        pl += tr_swz_xor<0x401F>(pl);
-        ps += tr_swz_xor<0x401F>(ps);
-        pl += tr_swz_xor<0x201F>(pl);
-        ps += tr_swz_xor<0x201F>(ps);
-        pl += tr_swz_xor<0x101F>(pl);
-        ps += tr_swz_xor<0x101F>(ps);
-        pl += tr_swz_xor<0x081F>(pl);
-        ps += tr_swz_xor<0x081F>(ps);
-        pl += tr_swz_xor<0x041F>(pl);
-        ps += tr_swz_xor<0x041F>(ps);
+        pl += wv_swz<0x401F>(pl);
+        ps += wv_swz<0x401F>(ps);
+        pl += wv_swz<0x201F>(pl);
+        ps += wv_swz<0x201F>(ps);
+        pl += wv_swz<0x101F>(pl);
+        ps += wv_swz<0x101F>(ps);
+        pl += wv_swz<0x081F>(pl);
+        ps += wv_swz<0x081F>(ps);
+        pl += wv_swz<0x041F>(pl);
+        ps += wv_swz<0x041F>(ps);
         if (o < NO) {
           const float b = sB[o];
           const float yh = (Rn > 0 ? pl + b : 0.f) + (Rs > 0 ? ps + b : 0.f);
@@ -590,7 +533,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
           lsum += (double)e * (double)e;
           if (out != nullptr) out[n * NO + o] = yh;
         }
-        spec_barrier();
+        wv_barrier();
         for (int e2 = t; e2 < NO * KR; e2 += kSpecT) {
           const int o = e2 / KR, r = e2 - o * KR;
           const float rv = sRv[o];
@@ -601,7 +544,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
         }
       }
     }
-    spec_barrier();
+    wv_barrier();
     // dZ_j / dV_j = sum_o residual_o * coefficient(o, j)  (one thread per coefficient column)
     if (t < Rn + Rs) {
       float dz = 0.f;
@@ -611,7 +554,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
         for (int o = 0; o < NO; ++o) dz = fmaf(sRv[o], sPC2[o * Rs + (t - Rn)], dz);
       sDZ[t] = dz;
     }
-    spec_barrier();
+    wv_barrier();
     TR_PROF_MARK(2);
     // dT_n in place and the A1 / C1 gradients, one (d, j) item per lane (all 512 lanes busy)
 #pragma unroll
@@ -657,7 +600,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
     }
     // y of the next sample (issued before this sample's DMA, so the counted waits stay exact)
     if (k + 1 < nr && t < NO) ycur = y[sample_of(k + 1) * NO + t];
-    spec_barrier();
+    wv_barrier();
     TR_PROF_MARK(3);
 
     // ---- gradient GEMM by row blocks: dPhi0[w, k] += sum_d X_n[w, d] dT_n[d, k] ----------------
@@ -694,7 +637,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
 #pragma unroll
             for (int v = 0; v < 4; ++v)
 #pragma unroll
-              for (int u = 0; u < KT; ++u) gacc[p][u][v & 1] = mfma4(xx[u][v], bb[v], gacc[p][u][v & 1]);
+              for (int u = 0; u < KT; ++u) gacc[p][u][v & 1] = wv_mfma_16x16x4(xx[u][v], bb[v], gacc[p][u][v & 1]);
           };
           ld(xA, bA, 0);
           for (int c = 0; c < nch; c += 2) {
@@ -710,7 +653,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
 #if TR_SPEC_PROFILE
           const unsigned long long w0 = __builtin_readcyclecounter();
 #endif
-          spec_barrier();  // every wave's reads of rows [RB*p, RB*(p+1)) have retired
+          wv_barrier();  // every wave's reads of rows [RB*p, RB*(p+1)) have retired
           cnt_blk[p] = issue(sample_of(k + 1), p);
 #if TR_SPEC_PROFILE
           prof[6] += __builtin_readcyclecounter() - w0;
@@ -764,7 +707,7 @@ __global__ __launch_bounds__(kSpecT) void k_spec_fused(
   // data loss partial: fixed-order block reduction (each output's thread accumulated its own)
   {
     double* dred = reinterpret_cast<double*>(lds + g.oRed);
-    const double ls = tr_wave_allreduce_d(lsum);
+    const double ls = wv_allreduce_d(lsum);
     __syncthreads();
     if (lane == 0) dred[wv] = ls;
     __syncthreads();

@@ -27,12 +27,6 @@
 
 namespace tr {
 
-typedef float sg_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ sg_f32x4 sg_mfma(float a, float b, sg_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 // ------------------------------------------------------------------------------------------
 // forward: T[n][d][k] = sum_w X[n][w][d] Phi0[w][k].  Workgroup (d group of 64, sample chunk):
 // wave v owns d tile 4*blockIdx.x + v and every k tile.  MFMA C[i=d][j=k]: lane (j, q) of a k step
@@ -55,9 +49,9 @@ __global__ __launch_bounds__(256) void k_specg_fwd(const float* __restrict__ X, 
   if (dt * 16 >= D) return;
   for (int64_t n = n0; n < n1; ++n) {
     const float* xs = X + n * xld;
-    sg_f32x4 acc[KTM];
+    wv_f4 acc[KTM];
 #pragma unroll
-    for (int t = 0; t < KTM; ++t) acc[t] = sg_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < KTM; ++t) acc[t] = wv_f4{0.f, 0.f, 0.f, 0.f};
     for (int w0 = 0; w0 < W; w0 += 16) {
       float a[4], b[4][KTM];
 #pragma unroll
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(256) void k_specg_fwd(const float* __restrict__ X, 
       for (int s = 0; s < 4; ++s)
 #pragma unroll
         for (int t = 0; t < KTM; ++t)
-          if (t < KT) acc[t] = sg_mfma(a[s], b[s][t], acc[t]);
+          if (t < KT) acc[t] = wv_mfma_16x16x4(a[s], b[s][t], acc[t]);
     }
     // C[i = d row][j = k col]: lane (j, q) reg r holds row 4q + r of the tile, column j
     float* tn = T + n * (int64_t)D * KP;
@@ -121,11 +115,11 @@ __global__ __launch_bounds__(64) void k_specg_fwd4(const float* __restrict__ X, 
   for (int64_t n = n0; n < n1; ++n) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(uintptr_t)(X + n * xld), (short)0, (int)((int64_t)W * D * 4), 0x00020000);
-    sg_f32x4 acc[KTM][4];
+    wv_f4 acc[KTM][4];
 #pragma unroll
     for (int t = 0; t < KTM; ++t)
 #pragma unroll
-      for (int m = 0; m < 4; ++m) acc[t][m] = sg_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int m = 0; m < 4; ++m) acc[t][m] = wv_f4{0.f, 0.f, 0.f, 0.f};
     // SG_U steps of 4 rows per batch, the next batch's loads issued before this batch's MFMAs: one
     // load in flight per wave left the loop waiting on memory latency (1.09 ms at (512, 129))
     constexpr int SG_U = 4;
@@ -133,7 +127,7 @@ __global__ __launch_bounds__(64) void k_specg_fwd4(const float* __restrict__ X, 
     bool kok[KTM];  // column k = 16 t + i of Phi0 exists (past K: the next row's values, masked)
 #pragma unroll
     for (int t = 0; t < KTM; ++t) kok[t] = 16 * t + i < K;
-    sg_f32x4 xb[2][SG_U];
+    wv_f4 xb[2][SG_U];
     float ab[2][SG_U][KTM];
     // (per-lane offsets fixed, the row in the scalar offset: no per-element address registers; rows
     // past W read zeros from both buffers' ranges, columns k >= K of Phi0 are masked)
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(64) void k_specg_fwd4(const float* __restrict__ X, 
 #pragma unroll
       for (int u = 0; u < SG_U; ++u) {
         const int wr = w0 + 4 * u;
-        xb[buf][u] = __builtin_bit_cast(sg_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, xvo, 4 * wr * D, 0));
+        xb[buf][u] = __builtin_bit_cast(wv_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, xvo, 4 * wr * D, 0));
 #pragma unroll
         for (int t = 0; t < KTM; ++t)  // (loaded unconditionally, masked by a select: a conditional
           // load compiles to a branch with a vmcnt(0) wait inside it, which serialised the loop)
@@ -156,7 +150,7 @@ __global__ __launch_bounds__(64) void k_specg_fwd4(const float* __restrict__ X, 
           if (d0 + m >= D) continue;  // (uniform: no lane's column d0 + 4 i + m exists; D = 129's tail)
           const float b = mok[m] ? xb[buf][u][m] : 0.f;
 #pragma unroll
-          for (int t = 0; t < KTM; ++t) acc[t][m] = sg_mfma(kok[t] ? ab[buf][u][t] : 0.f, b, acc[t][m]);
+          for (int t = 0; t < KTM; ++t) acc[t][m] = wv_mfma_16x16x4(kok[t] ? ab[buf][u][t] : 0.f, b, acc[t][m]);
         }
     };
     const int nbat = (W + 4 * SG_U - 1) / (4 * SG_U);
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(64) void k_specg_fwd4(const float* __restrict__ X, 
     for (int m = 0; m < 4; ++m)
       if (mok[m])
 #pragma unroll
-        for (int t = 0; t < KTM; ++t) *reinterpret_cast<sg_f32x4*>(tn + (int64_t)(db + m) * KP + t * 16 + 4 * q) = acc[t][m];
+        for (int t = 0; t < KTM; ++t) *reinterpret_cast<wv_f4*>(tn + (int64_t)(db + m) * KP + t * 16 + 4 * q) = acc[t][m];
   }
 }
 
@@ -250,7 +244,7 @@ __global__ __launch_bounds__(256) void k_specg_epi(int64_t N, SpecGeom g, const 
           v = fmaf(sT[dd * TS + j], ph, v);
         }
       }
-      v = tr_wave_allreduce(v);
+      v = wv_allreduce(v);
       if (lane == 0) sZV[j] = v;
     }
     __syncthreads();
@@ -350,7 +344,7 @@ __global__ __launch_bounds__(256) void k_specg_epi(int64_t N, SpecGeom g, const 
   for (int o = t; o < NO; o += NT) sl[g.offB + o] = sAcc[(D + NO) * R2 + o];
   // loss partial: fixed-order block reduction
   __shared__ double dred[4];
-  const double ls = tr_wave_allreduce_d(lsum);
+  const double ls = wv_allreduce_d(lsum);
   if (lane == 0) dred[wv] = ls;
   __syncthreads();
   if (t == 0) {
@@ -380,9 +374,9 @@ __global__ __launch_bounds__(256) void k_specg_bwd(const float* __restrict__ X, 
   const bool wok = w < W;
   const int64_t n0 = (int64_t)blockIdx.y * rows_per_blk;
   const int64_t n1 = n0 + rows_per_blk < N ? n0 + rows_per_blk : N;
-  sg_f32x4 acc[KTM];
+  wv_f4 acc[KTM];
 #pragma unroll
-  for (int tt = 0; tt < KTM; ++tt) acc[tt] = sg_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int tt = 0; tt < KTM; ++tt) acc[tt] = wv_f4{0.f, 0.f, 0.f, 0.f};
   if (wt * 16 < W) {
     for (int64_t n = n0; n < n1; ++n) {
       const float* xr = X + n * xld + (int64_t)(wok ? w : 0) * D;
@@ -405,7 +399,7 @@ __global__ __launch_bounds__(256) void k_specg_bwd(const float* __restrict__ X, 
           for (int tt = 0; tt < KTM; ++tt)
             if (tt < KT) {
               const float b = dd < D ? tn[(int64_t)dd * KP + tt * 16 + i] : 0.f;
-              acc[tt] = sg_mfma(a[m], b, acc[tt]);
+              acc[tt] = wv_mfma_16x16x4(a[m], b, acc[tt]);
             }
         }
       }
@@ -447,11 +441,11 @@ __global__ __launch_bounds__(256) void k_specg_bwd4(const float* __restrict__ X,
   const int i = lane & 15, q = lane >> 4;
   const int64_t n0 = (int64_t)blockIdx.y * rows_per_blk;
   const int64_t n1 = n0 + rows_per_blk < N ? n0 + rows_per_blk : N;
-  sg_f32x4 acc[NWT][KTM];
+  wv_f4 acc[NWT][KTM];
 #pragma unroll
   for (int h = 0; h < NWT; ++h)
 #pragma unroll
-    for (int tt = 0; tt < KTM; ++tt) acc[h][tt] = sg_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int tt = 0; tt < KTM; ++tt) acc[h][tt] = wv_f4{0.f, 0.f, 0.f, 0.f};
   int xvo[NWT];  // rows past W: out of range, zero
 #pragma unroll
   for (int h = 0; h < NWT; ++h) {
@@ -466,7 +460,7 @@ __global__ __launch_bounds__(256) void k_specg_bwd4(const float* __restrict__ X,
           (void*)(uintptr_t)(X + n * xld), (short)0, (int)((int64_t)W * D * 4), 0x00020000);
       const __amdgpu_buffer_rsrc_t ts = __builtin_amdgcn_make_buffer_rsrc(
           (void*)(uintptr_t)(T + n * (int64_t)D * KP), (short)0, (int)((int64_t)D * KP * 4), 0x00020000);
-      sg_f32x4 xb[2][SG_UB][NWT];
+      wv_f4 xb[2][SG_UB][NWT];
       float bb[2][SG_UB][4][KTM];
       auto load_batch = [&](int s0, int buf) {
 #pragma unroll
@@ -474,7 +468,7 @@ __global__ __launch_bounds__(256) void k_specg_bwd4(const float* __restrict__ X,
           const int d0 = 16 * (s0 + u);
 #pragma unroll
           for (int h = 0; h < NWT; ++h)
-            xb[buf][u][h] = __builtin_bit_cast(sg_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xs, xvo[h], 4 * d0, 0));
+            xb[buf][u][h] = __builtin_bit_cast(wv_f4, __builtin_amdgcn_raw_buffer_load_b128(xs, xvo[h], 4 * d0, 0));
 #pragma unroll
           for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -492,7 +486,7 @@ __global__ __launch_bounds__(256) void k_specg_bwd4(const float* __restrict__ X,
             for (int h = 0; h < NWT; ++h) {
               const float a = db + m < D ? xb[buf][u][h][m] : 0.f;  // (a quad straddling D: the next row's values)
 #pragma unroll
-              for (int tt = 0; tt < KTM; ++tt) acc[h][tt] = sg_mfma(a, bb[buf][u][m][tt], acc[h][tt]);
+              for (int tt = 0; tt < KTM; ++tt) acc[h][tt] = wv_mfma_16x16x4(a, bb[buf][u][m][tt], acc[h][tt]);
             }
         }
       };

@@ -39,6 +39,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "tr_bf16_split.h"
 #include "tr_common.h"
 #include "tr_spectral.h"
 
@@ -86,7 +87,6 @@ __device__ unsigned long long g_slice_prof[256][8][8];  // [workgroup][wave][pha
 #endif
 
 namespace {
-typedef float sl_f4 __attribute__((ext_vector_type(4)));
 typedef float sl_f2 __attribute__((ext_vector_type(2)));
 constexpr int SL_NW = 8;
 constexpr int SL_T = SL_NW * TR_WAVE;
@@ -110,8 +110,7 @@ static_assert(SL_O_TP % 8 == 0 && SL_O_PART % 8 == 0, "the per-wave partial rows
 // LDS round trip, not eight dependent ones), summed in wave order from 0 like the running sums
 // they replace
 __device__ __forceinline__ float sl_sum8(const float* p) {
-  typedef float f4_t __attribute__((ext_vector_type(4)));
-  const f4_t a = *reinterpret_cast<const f4_t*>(p), b = *reinterpret_cast<const f4_t*>(p + 4);
+  const wv_f4 a = *reinterpret_cast<const wv_f4*>(p), b = *reinterpret_cast<const wv_f4*>(p + 4);
   float s = 0.f;
   s += a[0];
   s += a[1];
@@ -123,60 +122,29 @@ __device__ __forceinline__ float sl_sum8(const float* p) {
   s += b[3];
   return s;
 }
-__device__ __forceinline__ sl_f4 sl_mfma(float a, float b, sl_f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // ---- round-to-nearest bf16 split (SP > 0) --------------------------------------------------
-// x = x1 + x2 + x3 by round-to-nearest-even bf16 conversions (v_cvt_pk_bf16_f32, two values per
-// instruction): x1 = bf16(x), r = x - x1 (exact: Sterbenz), x2 = bf16(r), x3 = r - x2 (exact, at
-// most 8 significant bits: exactly a bf16), for every finite |x| below the bf16 overflow
-// threshold (3.39e38) and above 2^-100.  |x2| <= 2^-8 |x|, |x3| <= 2^-17 |x|, and — unlike a
-// truncating split, whose pieces all carry the sign of x — the pieces' signs are independent of
-// x.  The factor side (Phi0 fragments, dT) is always split in three.  The sample side X is split
+// The three-piece split x = x1 + x2 + x3 and its derivation are in tr_bf16_split.h.  The factor
+// side (Phi0 fragments, dT) is always split in three.  The sample side X is split
 // in two by default (SL_XP(SP) == 2: x1 + x2, |x - x1 - x2| < 2^-16 |x|, measured maximum 2^-17.0,
 // median 2^-19.4, unbiased) and a product x.f is formed as the five cross terms x1f1, x1f2, x2f1,
 // x1f3, x2f2; with TR_SLICE_XPIECES=3 (SP 3, 4) X is split in three as well and the six terms of
 // weight >= 2^-17 are formed (x3f1 added), the dropped x2f3 + x3f2 + x3f3 weighing < 2^-24 |xf|
 // (measured maximum 2^-24.3, median 2^-29).  Every term is an exact bf16 x bf16 product in the
-// fp32 accumulator of v_mfma_f32_16x16x32_bf16 (16x the f32 MFMA rate).  At full config-5 size
+// fp32 accumulator of v_mfma_f32_16x16x32_bf16.  At full config-5 size
 // the default form's gradients lie within 3.5e-7 of fp64 (the reference's own fp32 op sequence:
-// 0.6-4.2e-6; a truncating split's dropped terms are biased toward the sign of the product, and
-// over config 5's sums that bias reached 8-25x the f32 MFMA form's error).
-// tests/test_split_numerics.py holds these bounds, tests/test_gpu_fullsize.py the full-size errors.
-typedef __bf16 sl_bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 sl_bf2 __attribute__((ext_vector_type(2)));
-typedef uint32_t sl_u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ sl_f4 sl_mfma_bf(sl_u4 a, sl_u4 b, sl_f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(sl_bf8, a), __builtin_bit_cast(sl_bf8, b), c, 0,
-                                                 0, 0);
-}
-// two values -> one VGPR of packed RNE bf16 (element 0 = a in the low half), v_cvt_pk_bf16_f32
-__device__ __forceinline__ uint32_t sl_pack_rne(float a, float b) {
-  return __builtin_bit_cast(uint32_t, sl_bf2{(__bf16)a, (__bf16)b});
-}
-// the two halves of a packed pair back as fp32 values (the low half by a byte permute: a shift of
-// the packed word lets the compiler re-convert that value alone, one more cvt per pair)
-__device__ __forceinline__ float sl_lo_f32(uint32_t h) { return __uint_as_float(__builtin_amdgcn_perm(h, h, 0x01000c0cu)); }
-__device__ __forceinline__ float sl_hi_f32(uint32_t h) { return __uint_as_float(h & 0xffff0000u); }
+// 0.6-4.2e-6).  tests/test_gpu_fullsize.py holds the full-size errors.
 // split a (element 2m) and b (element 2m+1) into the three packed bf16 pairs of VGPR m
 #ifndef TR_SLICE_SPLITMODE
-#define TR_SLICE_SPLITMODE 2  // 2: x1, x2, x3 all by round-to-nearest (above); 1: x1 truncated, x2 / x3 by
+#define TR_SLICE_SPLITMODE 2  // 2: x1, x2, x3 all by round-to-nearest (bfs_split2); 1: x1 truncated, x2 / x3 by
                               // round-to-nearest (unbiased too, dropped terms < 2^-22 |ab|); 0: all
                               // truncated (round 3: dropped terms biased toward the sign of ab)
 #endif
-__device__ __forceinline__ void sl_split2(float a, float b, uint32_t& h1, uint32_t& h2, uint32_t& h3) {
-  float ra, rb;
-  if (TR_SLICE_SPLITMODE == 2) {
-    h1 = sl_pack_rne(a, b);
-    ra = a - sl_lo_f32(h1);
-    rb = b - sl_hi_f32(h1);
-  } else {
-    const uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
-    h1 = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-    ra = a - __uint_as_float(ua & 0xffff0000u);
-    rb = b - __uint_as_float(ub & 0xffff0000u);
-  }
+__device__ __forceinline__ void sl_split_pair(float a, float b, uint32_t& h1, uint32_t& h2, uint32_t& h3) {
+  if (TR_SLICE_SPLITMODE == 2) return bfs_split2(a, b, h1, h2, h3);
+  const uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
+  h1 = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
+  const float ra = a - __uint_as_float(ua & 0xffff0000u), rb = b - __uint_as_float(ub & 0xffff0000u);
   if (TR_SLICE_SPLITMODE == 0) {
     const uint32_t ura = __float_as_uint(ra), urb = __float_as_uint(rb);
     h2 = __builtin_amdgcn_perm(urb, ura, 0x07060302u);
@@ -184,13 +152,12 @@ __device__ __forceinline__ void sl_split2(float a, float b, uint32_t& h1, uint32
     h3 = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
     return;
   }
-  h2 = sl_pack_rne(ra, rb);
-  const float sa = ra - sl_lo_f32(h2), sb = rb - sl_hi_f32(h2);
-  h3 = sl_pack_rne(sa, sb);
+  h2 = bfs_pack_rne(ra, rb);
+  h3 = bfs_pack_rne(ra - bfs_lo_f32(h2), rb - bfs_hi_f32(h2));
 }
-__device__ __forceinline__ void sl_split_m(float a, float b, sl_u4 (&f)[3], int m) {
+__device__ __forceinline__ void sl_split_m(float a, float b, wv_u4 (&f)[3], int m) {
   uint32_t h1, h2, h3;
-  sl_split2(a, b, h1, h2, h3);
+  sl_split_pair(a, b, h1, h2, h3);
   f[0][m] = h1;
   f[1][m] = h2;
   f[2][m] = h3;
@@ -204,35 +171,35 @@ __device__ __forceinline__ void sl_split_m(float a, float b, sl_u4 (&f)[3], int 
 // (tests/test_gpu_fullsize.py), both forms' gradients sit within 1.7-3.5e-7 normwise, the f32
 // MFMA form's within 1.1e-7 and the reference's own fp32 op sequence on the CPU within 0.6-4.2e-6.
 template <int XP>
-__device__ __forceinline__ void sl_splitx_m(float a, float b, sl_u4 (&f)[3], int m) {
+__device__ __forceinline__ void sl_splitx_m(float a, float b, wv_u4 (&f)[3], int m) {
   if constexpr (XP == 2) {
-    const uint32_t h1 = sl_pack_rne(a, b);
+    const uint32_t h1 = bfs_pack_rne(a, b);
     f[0][m] = h1;
-    f[1][m] = sl_pack_rne(a - sl_lo_f32(h1), b - sl_hi_f32(h1));
+    f[1][m] = bfs_pack_rne(a - bfs_lo_f32(h1), b - bfs_hi_f32(h1));
   } else {
     sl_split_m(a, b, f, m);
   }
 }
 // c += A.B over the six cross terms of weight >= 2^-17 (A in XP pieces, B in three)
 template <int XP>
-__device__ __forceinline__ sl_f4 sl_mfma6(const sl_u4 (&a)[3], const sl_u4 (&b)[3], sl_f4 c) {
-  if constexpr (XP == 3) c = sl_mfma_bf(a[2], b[0], c);
-  c = sl_mfma_bf(a[1], b[1], c);
-  c = sl_mfma_bf(a[0], b[2], c);
-  c = sl_mfma_bf(a[1], b[0], c);
-  c = sl_mfma_bf(a[0], b[1], c);
-  c = sl_mfma_bf(a[0], b[0], c);
+__device__ __forceinline__ wv_f4 sl_mfma6(const wv_u4 (&a)[3], const wv_u4 (&b)[3], wv_f4 c) {
+  if constexpr (XP == 3) c = wv_mfma_bf16(a[2], b[0], c);
+  c = wv_mfma_bf16(a[1], b[1], c);
+  c = wv_mfma_bf16(a[0], b[2], c);
+  c = wv_mfma_bf16(a[1], b[0], c);
+  c = wv_mfma_bf16(a[0], b[1], c);
+  c = wv_mfma_bf16(a[0], b[0], c);
   return c;
 }
 // packed lin columns (Rn <= 8): B = [b1 | b2] (lanes 0-7 | 8-15) and [b3 | 0]; column c of the
 // product is the sum of accumulator columns c and c + 8 (folded by sl_fold8): four MFMAs for
 // the six cross terms (a3b2 comes along), three with a two-piece A
 template <int XP>
-__device__ __forceinline__ sl_f4 sl_mfma_lp(const sl_u4 (&a)[3], const sl_u4 (&b)[2], sl_f4 c) {
-  if constexpr (XP == 3) c = sl_mfma_bf(a[2], b[0], c);
-  c = sl_mfma_bf(a[0], b[1], c);
-  c = sl_mfma_bf(a[1], b[0], c);
-  c = sl_mfma_bf(a[0], b[0], c);
+__device__ __forceinline__ wv_f4 sl_mfma_lp(const wv_u4 (&a)[3], const wv_u4 (&b)[2], wv_f4 c) {
+  if constexpr (XP == 3) c = wv_mfma_bf16(a[2], b[0], c);
+  c = wv_mfma_bf16(a[0], b[1], c);
+  c = wv_mfma_bf16(a[1], b[0], c);
+  c = wv_mfma_bf16(a[0], b[0], c);
   return c;
 }
 // SP (the kernel's GEMM form): 0 f32 MFMA; 1 / 2 bf16 split with a two-piece X, lin columns
@@ -256,40 +223,9 @@ __device__ __forceinline__ sl_f4 sl_mfma_lp(const sl_u4 (&a)[3], const sl_u4 (&b
 // per-sample gradient accumulators: forms 3-6 with tail rows (without them, D <= 128, the
 // accumulator temporaries push the kernel past 256 VGPRs into scratch)
 #define SL_ACC(SP, DT) (TR_SLICE_ACCUM && (SP) >= 3 && (DT) > 0)
-template <int CTRL>
-__device__ __forceinline__ float sl_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-// 16-lane row sum (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror): every lane of
-// the row ends with the bitwise-identical value
-__device__ __forceinline__ float sl_row_sum16(float v) {
-  v += sl_dpp<0xB1>(v);
-  v += sl_dpp<0x4E>(v);
-  v += sl_dpp<0x141>(v);
-  v += sl_dpp<0x140>(v);
-  return v;
-}
-// xor-16 / xor-32 butterfly steps by v_permlane16/32_swap (no LDS round trip)
-__device__ __forceinline__ float sl_xor16(float v) {
-  const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
-}
-__device__ __forceinline__ float sl_xor32(float v) {
-  const auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
-}
-__device__ __forceinline__ float sl_groups_sum(float v) { return sl_xor32(sl_xor16(v)); }
+__device__ __forceinline__ float sl_groups_sum(float v) { return wv_xor32_sum(wv_xor16_sum(v)); }
 // lanes i and i ^ 8 of each 16-lane row summed (row_ror:8); both end with the same value
-__device__ __forceinline__ float sl_fold8(float v) { return v + sl_dpp<0x128>(v); }
-// barrier that leaves LDS-DMA in flight (__syncthreads() would wait vmcnt(0))
-__device__ __forceinline__ void sl_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ uint32_t sl_lds_addr(const float* p) {
-  return (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) float*)p);
-}
+__device__ __forceinline__ float sl_fold8(float v) { return v + wv_dpp<0x128>(v); }
 // sl_dma16b with soffset = tstr * q and the LDS address lds_b + lds_off formed by the statement
 // itself from a base and constants (formed outside, the compiler hoisted all sixteen out of the
 // sample loop into SGPRs the kernel does not have: one spill reload per piece)
@@ -300,22 +236,6 @@ __device__ __forceinline__ void sl_dma16bq(__amdgpu_buffer_rsrc_t rs, uint32_t t
                : "=&s"(keep), "=&s"(so)
                : "v"(voff), "s"(lds_b), "s"(tstr), "s"(q), "s"(rs), "s"(lds_off)
                : "memory", "scc");
-}
-// one 4-B LDS-DMA piece per lane: gsrc -> LDS byte address m0 + 4 * lane (m0 saved / restored)
-__device__ __forceinline__ void sl_dma4(const float* gsrc, const float* lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(sl_lds_addr(lds_dst)))
-               : "memory");
-}
-// one 16-B LDS-DMA piece per lane: gsrc (4-B aligned is enough) -> LDS byte address m0 + 16 * lane
-__device__ __forceinline__ void sl_dma16(const float* gsrc, const float* lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(sl_lds_addr(lds_dst)))
-               : "memory");
 }
 // one 16-B LDS-DMA piece per lane through a buffer descriptor: rsrc base + soff + voff (lane) -> LDS
 // byte address m0 + 16 * lane; no per-lane 64-bit address arithmetic at the call
@@ -336,21 +256,6 @@ __device__ __forceinline__ void sl_dma16b(__amdgpu_buffer_rsrc_t rs, uint32_t so
                : "=&s"(keep)
                : "v"(voff), "s"(rs), "s"(lds_b), "s"(soff)
                : "memory");
-}
-// s_waitcnt vmcnt(n), n wave-uniform in [0, 63]
-__device__ __forceinline__ void sl_wait_vm(int n) {
-#define SL_VM(k) \
-  case k:        \
-    asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); \
-    break;
-#define SL_VM8(b) SL_VM(b) SL_VM(b + 1) SL_VM(b + 2) SL_VM(b + 3) SL_VM(b + 4) SL_VM(b + 5) SL_VM(b + 6) SL_VM(b + 7)
-  switch (n < 0 ? 0 : n) {
-    SL_VM8(0) SL_VM8(8) SL_VM8(16) SL_VM8(24) SL_VM8(32) SL_VM8(40) SL_VM8(48) SL_VM8(56)
-    default:
-      asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-  }
-#undef SL_VM8
-#undef SL_VM
 }
 // this lane's index recomputed where it is used (v_mbcnt, not a register held across the sample
 // loop: at 256 VGPRs the compiler spilled the held lane index, and each reload's vmcnt(0) wait
@@ -391,9 +296,9 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
   const int dbase = 32 * p;    // first d of this wave's pair
 
   float* slice = lds + wv * SL_SLICE;
-  const uint32_t slice_b = (uint32_t)__builtin_amdgcn_readfirstlane(sl_lds_addr(slice));  // its LDS byte address
+  const uint32_t slice_b = (uint32_t)__builtin_amdgcn_readfirstlane(wv_lds_addr(slice));  // its LDS byte address
   float* sTail = lds + SL_O_TAIL + wv * SL_TAIL;  // [Dt][TR]
-  const uint32_t tail_b = (uint32_t)__builtin_amdgcn_readfirstlane(sl_lds_addr(sTail));
+  const uint32_t tail_b = (uint32_t)__builtin_amdgcn_readfirstlane(wv_lds_addr(sTail));
   float* sEx = lds + SL_O_EX;                      // [8 waves][64 lanes][8]
   float* sTP = lds + SL_O_TP;                      // [2 rows][32 columns][8 waves]
   float* sPart = lds + SL_O_PART;                  // [Z 16 | V 16][8 waves]
@@ -428,7 +333,7 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
   // + gq of the half, the same w for A and B); bs = spectral columns, bl = lin columns
   constexpr int NSP = SP ? SL_STEPS / 8 : 1;
   constexpr int NL = SL_LP(SP) ? 2 : 3;
-  sl_u4 bs[NSP][3], bl[NSP][NL];
+  wv_u4 bs[NSP][3], bl[NSP][NL];
   if constexpr (!SP) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -447,7 +352,7 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
         sl_split_m((i < RC && ok0) ? Phi0[w0 * K + Rn + i] : 0.f, (i < RC && ok1) ? Phi0[w1 * K + Rn + i] : 0.f, bs[S],
                    m);
         uint32_t h1, h2, h3;
-        sl_split2((cl < Rn && ok0) ? Phi0[w0 * K + cl] : 0.f, (cl < Rn && ok1) ? Phi0[w1 * K + cl] : 0.f, h1, h2, h3);
+        sl_split_pair((cl < Rn && ok0) ? Phi0[w0 * K + cl] : 0.f, (cl < Rn && ok1) ? Phi0[w1 * K + cl] : 0.f, h1, h2, h3);
         if constexpr (SL_LP(SP)) {
           bl[S][0][m] = i < 8 ? h1 : h2;
           bl[S][1][m] = i < 8 ? h3 : 0u;
@@ -458,11 +363,11 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
         }
       }
   }
-  sl_f4 gacc[SL_TILES][2];
+  wv_f4 gacc[SL_TILES][2];
 #pragma unroll
   for (int q = 0; q < SL_TILES; ++q) {
-    gacc[q][0] = sl_f4{0.f, 0.f, 0.f, 0.f};
-    gacc[q][1] = sl_f4{0.f, 0.f, 0.f, 0.f};
+    gacc[q][0] = wv_f4{0.f, 0.f, 0.f, 0.f};
+    gacc[q][1] = wv_f4{0.f, 0.f, 0.f, 0.f};
   }
   float an1[2][4], as1[4];  // dPhi(A1) partial (both d tiles), dPhi(C1) (own tile h = hw)
 #pragma unroll
@@ -547,7 +452,7 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
     } else if (ln < Dt * TR) {  // lane -> (row 128 + lane / TR, w offset lane % TR)
       const int tr = ln / TR, wo = ln - tr * TR;
       const int64_t w = wbase + TR * p + wo;
-      sl_dma4(X + n * xld + (w < g.W ? w : 0) * D + 128 + tr, sTail);  // (rows past W: any valid row, times zero)
+      wv_dma4<WV_CACHED, WV_DST_RFL>(X + n * xld + (w < g.W ? w : 0) * D + 128 + tr, sTail);  // (rows past W: any valid row, times zero)
     }
   };
   // split kernels: wave p's tail goes out right after its pieces of tile qt = TQ p + TQ - 1 (the
@@ -583,14 +488,14 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
     const int64_t nn = has_next ? sample_of(k + 1) : n;
 
     // ---- forward: T (tile jt, d tile h) over this wave's half ---------------------------
-    sl_f4 T00 = {0.f, 0.f, 0.f, 0.f}, T01 = T00, T10 = T00, T11 = T00;
+    wv_f4 T00 = {0.f, 0.f, 0.f, 0.f}, T01 = T00, T10 = T00, T11 = T00;
     // tail rows d = 128 + tr: VALU partial over this wave's tail steps [SQ p, SQ (p + 1)) inside
     // the forward loop (bf0 / bf1 of the step are in hand), reduced over lane groups after it
     float ta[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
-    sl_f4 Tts = {0.f, 0.f, 0.f, 0.f}, Ttl = Tts;  // split mode: tail rows (row tr = lane group 0, reg tr)
+    wv_f4 Tts = {0.f, 0.f, 0.f, 0.f}, Ttl = Tts;  // split mode: tail rows (row tr = lane group 0, reg tr)
     {
       sl_f2 xa[4], xb[4];
-      sl_u4 xf[2][3];  // split mode: the k step's A fragments of d tiles 0 / 1
+      wv_u4 xf[2][3];  // split mode: the k step's A fragments of d tiles 0 / 1
       int fo[4];
       {
         const int L = sl_lane_now();
@@ -599,7 +504,7 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
       }
       {
         SL_SUB_BEGIN();
-        sl_wait_vm((ntl - 1) * 2 + NTL);
+        wv_wait_vm<63>((ntl - 1) * 2 + NTL);
         SL_SUB_END(1);
       }
 #pragma unroll
@@ -609,7 +514,7 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
         if (q + 1 < ntl) {
           {
             SL_SUB_BEGIN();
-            sl_wait_vm((ntl - 2 - q) * 2 + (q + 1 <= qt ? NTL : 0));
+            wv_wait_vm<63>((ntl - 2 - q) * 2 + (q + 1 <= qt ? NTL : 0));
             SL_SUB_END(1);
           }
 #pragma unroll
@@ -619,10 +524,10 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
         if constexpr (!SP) {
 #pragma unroll
           for (int s = 0; s < 4 && !(TR_SLICE_SKIP & 2); ++s) {
-            T00 = sl_mfma(xa[s].x, bf0[4 * q + s], T00);
-            T01 = sl_mfma(xa[s].y, bf0[4 * q + s], T01);
-            T10 = sl_mfma(xa[s].x, bf1[4 * q + s], T10);
-            T11 = sl_mfma(xa[s].y, bf1[4 * q + s], T11);
+            T00 = wv_mfma_16x16x4(xa[s].x, bf0[4 * q + s], T00);
+            T01 = wv_mfma_16x16x4(xa[s].y, bf0[4 * q + s], T01);
+            T10 = wv_mfma_16x16x4(xa[s].x, bf1[4 * q + s], T10);
+            T11 = wv_mfma_16x16x4(xa[s].y, bf1[4 * q + s], T11);
           }
         } else {
           // tile q holds elements 4 (q & 1) .. +3 of k step q / 2: VGPRs 2 (q & 1), 2 (q & 1) + 1
@@ -686,15 +591,15 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
         // tail rows d = 128 + tr over this wave's tail k step (S = p): A row i = tail row i
         // (rows >= Dt zero), element j <-> w offset 4 j + gq of the wave's 32 tail w (after the
         // loop: nothing of the forward is live; one case per static S)
-        sl_u4 tf[3];
-        if (NTL) sl_wait_vm(0);  // the tail (issued after the tiles) has landed
+        wv_u4 tf[3];
+        if (NTL) wv_wait_vm<63>(0);  // the tail (issued after the tiles) has landed
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           const float x0 = i < Dt ? sTail[i * TR + 8 * m + gq] : 0.f;
           const float x1 = i < Dt ? sTail[i * TR + 8 * m + 4 + gq] : 0.f;
           sl_splitx_m<SL_XPF(SP)>(x0, x1, tf, m);
         }
-        auto tail_step = [&](const sl_u4(&b_s)[3], const sl_u4(&b_l)[NL]) {
+        auto tail_step = [&](const wv_u4(&b_s)[3], const wv_u4(&b_l)[NL]) {
           Tts = sl_mfma6<SL_XPF(SP)>(tf, b_s, Tts);
           if constexpr (SL_LP(SP))
             Ttl = sl_mfma_lp<SL_XPF(SP)>(tf, b_l, Ttl);
@@ -727,15 +632,15 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
     }
     SL_MARK(0);
     // ---- exchange the spectral tiles with the partner half ---------------------------------
-    *reinterpret_cast<sl_f4*>(sEx + (wv * TR_WAVE + lk) * 8) = T00;
-    *reinterpret_cast<sl_f4*>(sEx + (wv * TR_WAVE + lk) * 8 + 4) = T01;
+    *reinterpret_cast<wv_f4*>(sEx + (wv * TR_WAVE + lk) * 8) = T00;
+    *reinterpret_cast<wv_f4*>(sEx + (wv * TR_WAVE + lk) * 8 + 4) = T01;
     SL_MARK(2);
-    sl_barrier();
+    wv_barrier();
     SL_MARK(3);
     {
       const float* pe = sEx + ((wv ^ 4) * TR_WAVE + lk) * 8;
-      T00 += *reinterpret_cast<const sl_f4*>(pe);  // two-term sums commute: both halves hold
-      T01 += *reinterpret_cast<const sl_f4*>(pe + 4);  // the bitwise-identical full tile
+      T00 += *reinterpret_cast<const wv_f4*>(pe);  // two-term sums commute: both halves hold
+      T01 += *reinterpret_cast<const wv_f4*>(pe + 4);  // the bitwise-identical full tile
     }
     // full tail row values: lane (i, gq < Dt) holds T[128 + gq][spectral i] / [lin i]
     float tt0 = 0.f, tt1 = 0.f;
@@ -750,8 +655,8 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
     // tile h = hw, full T) -- nothing but the two sums stays live across barrier B -------------
     auto norm_of = [&](float x) {  // || T[d, spectral group of this lk] ||
       float sq = x * x;
-      if (CC >= 2) sq += sl_dpp<0xB1>(sq);
-      if (CC >= 4) sq += sl_dpp<0x4E>(sq);
+      if (CC >= 2) sq += wv_dpp<0xB1>(sq);
+      if (CC >= 4) sq += wv_dpp<0x4E>(sq);
       return __builtin_amdgcn_sqrtf(sq);
     };
     // table offsets from an opaque copy of the lane index: recomputed here (a few VALU ops)
@@ -765,7 +670,7 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
     // and meets zero factors: T columns past Rn are zero, and dz / dv are zeroed there, so only
     // the lin column partial needs one mask — the packed form's lanes 8-15 hold folded columns)
     auto tab8 = [&](const float* tb, int off, float (&o)[2][4]) {
-      const sl_f4 lo = *reinterpret_cast<const sl_f4*>(tb + off), hi = *reinterpret_cast<const sl_f4*>(tb + off + 4);
+      const wv_f4 lo = *reinterpret_cast<const wv_f4*>(tb + off), hi = *reinterpret_cast<const wv_f4*>(tb + off + 4);
 #pragma unroll
       for (int v = 0; v < 4; ++v)
 #pragma unroll
@@ -806,7 +711,7 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
       if (vlane) sPart[(16 + rs) * SL_NW + wv] = vp;
     }
     SL_MARK(4);
-    sl_barrier();
+    wv_barrier();
     SL_MARK(5);
 
     // ---- Z / V, y_hat, residual, dZ / dV (every wave, identical order) ----------------------
@@ -818,8 +723,8 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
     // output o with target yo: y_hat, residual, its dZ / dV terms, the bookkeeping wave's sums
     auto out_step = [&](int o, float yo) {
       const float ca = sCA[o * 16 + i], cc = sCC[o * 16 + i];
-      const float pl = sl_row_sum16(ca * zi);
-      const float ps = sl_row_sum16(cc * vi);
+      const float pl = wv_row_sum16(ca * zi);
+      const float ps = wv_row_sum16(cc * vi);
       const float b = sB[o];
       const float yh = (Rn > 0 ? pl + b : 0.f) + (Rs > 0 ? ps + b : 0.f);
       const float e = yh - yo;
@@ -896,13 +801,13 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
       }
       // split mode: B fragments of dT (element 2v + h of lane group g = d row 8g + 2v + h of the
       // pair: spectral T0h[v], lin T1h[v])
-      sl_u4 ds[3], dl[NL];
+      wv_u4 ds[3], dl[NL];
       if constexpr (SP) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           sl_split_m(T00[v], T01[v], ds, v);
           uint32_t h1, h2, h3;
-          sl_split2(T10[v], T11[v], h1, h2, h3);
+          sl_split_pair(T10[v], T11[v], h1, h2, h3);
           if constexpr (SL_LP(SP)) {  // lanes 8-15 take the second part of column i - 8
             const uint32_t h2r = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h2, 0x128, 0xF, 0xF, false);
             dl[0][v] = i < 8 ? h1 : h2r;
@@ -915,28 +820,28 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
         }
       }
       // the next tile's operand reads go out before this tile's MFMAs
-      sl_f4 pa = *reinterpret_cast<const sl_f4*>(slice + bo0);
-      sl_f4 pb = *reinterpret_cast<const sl_f4*>(slice + bo1);
+      wv_f4 pa = *reinterpret_cast<const wv_f4*>(slice + bo0);
+      wv_f4 pb = *reinterpret_cast<const wv_f4*>(slice + bo1);
 #pragma unroll
       for (int q = 0; q < SL_TILES; ++q) {
         if (q < ntl) {
-          const sl_f4 va = pa, vb = pb;
+          const wv_f4 va = pa, vb = pb;
           if (q + 1 < ntl) {
-            pa = *reinterpret_cast<const sl_f4*>(slice + 512 * (q + 1) + bo0);
-            pb = *reinterpret_cast<const sl_f4*>(slice + 512 * (q + 1) + bo1);
+            pa = *reinterpret_cast<const wv_f4*>(slice + 512 * (q + 1) + bo0);
+            pb = *reinterpret_cast<const wv_f4*>(slice + 512 * (q + 1) + bo1);
           }
           // the tile's two LDS-DMA pieces of the next sample go out between its MFMAs (after
           // the reads landed), not back to back: bursts stall on the memory issue queue
           if constexpr (!SP) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-              const sl_f4& src = v < 2 ? va : vb;
+              const wv_f4& src = v < 2 ? va : vb;
               const float a0 = src[2 * (v & 1) + 0], a1 = src[2 * (v & 1) + 1];
               if (!(TR_SLICE_SKIP & 4)) {
-                gacc[q][0] = sl_mfma(a0, T00[v], gacc[q][0]);
-                gacc[q][1] = sl_mfma(a0, T10[v], gacc[q][1]);
-                gacc[q][0] = sl_mfma(a1, T01[v], gacc[q][0]);
-                gacc[q][1] = sl_mfma(a1, T11[v], gacc[q][1]);
+                gacc[q][0] = wv_mfma_16x16x4(a0, T00[v], gacc[q][0]);
+                gacc[q][1] = wv_mfma_16x16x4(a0, T10[v], gacc[q][1]);
+                gacc[q][0] = wv_mfma_16x16x4(a1, T01[v], gacc[q][0]);
+                gacc[q][1] = wv_mfma_16x16x4(a1, T11[v], gacc[q][1]);
               }
               if (has_next && (v & 1)) {
                 if (v == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // tile q's reads landed
@@ -946,10 +851,10 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
             }
           } else {
             // A fragments: element 2v + h = X[w, d of (v, h)] (the order dT is held in)
-            sl_u4 af[3];
+            wv_u4 af[3];
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-              const sl_f4& src = v < 2 ? va : vb;
+              const wv_f4& src = v < 2 ? va : vb;
               sl_splitx_m<SL_XP(SP)>(src[2 * (v & 1) + 0], src[2 * (v & 1) + 1], af, v);
             }
             // the reads of tile q and q + 1 have landed at this wait: the next sample's pieces of
@@ -966,7 +871,7 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
             }
             if (!(TR_SLICE_SKIP & 4)) {
               if constexpr (SL_ACC(SP, DT))
-                gacc[q][0] += sl_mfma6<SL_XP(SP)>(af, ds, sl_f4{0.f, 0.f, 0.f, 0.f});
+                gacc[q][0] += sl_mfma6<SL_XP(SP)>(af, ds, wv_f4{0.f, 0.f, 0.f, 0.f});
               else
                 gacc[q][0] = sl_mfma6<SL_XP(SP)>(af, ds, gacc[q][0]);
             }
@@ -975,8 +880,8 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
               if (TAIL_LAST && Dt > 0 && q + 1 == qt) dma_tail(nn);
             }
             if (!(TR_SLICE_SKIP & 4)) {
-              const sl_f4 c1 = SL_ACC(SP, DT) ? sl_f4{0.f, 0.f, 0.f, 0.f} : gacc[q][1];
-              sl_f4 r1;
+              const wv_f4 c1 = SL_ACC(SP, DT) ? wv_f4{0.f, 0.f, 0.f, 0.f} : gacc[q][1];
+              wv_f4 r1;
               if constexpr (SL_LP(SP))
                 r1 = sl_mfma_lp<SL_XP(SP)>(af, dl, c1);
               else
@@ -985,8 +890,8 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
             }
           }
           if (Dt > 0 && q / TQ == p) {
-            gacc[q][0] = sl_mfma(at[q % TQ], dTt0, gacc[q][0]);
-            gacc[q][1] = sl_mfma(at[q % TQ], dTt1, gacc[q][1]);
+            gacc[q][0] = wv_mfma_16x16x4(at[q % TQ], dTt0, gacc[q][0]);
+            gacc[q][1] = wv_mfma_16x16x4(at[q % TQ], dTt1, gacc[q][1]);
           }
         }
       }
@@ -1014,9 +919,9 @@ __global__ __launch_bounds__(SL_T) void k_spec_slice(
 #pragma unroll
   for (int q = 0; q < SL_TILES; ++q)
 #pragma unroll
-    for (int jt = 0; jt < 2; ++jt) *reinterpret_cast<sl_f4*>(slice + ((q * 2 + jt) * TR_WAVE + lp) * 4) = gacc[q][jt];
-  *reinterpret_cast<sl_f4*>(sEx + (wv * TR_WAVE + lp) * 8) = sl_f4{an1[0][0], an1[0][1], an1[0][2], an1[0][3]};
-  *reinterpret_cast<sl_f4*>(sEx + (wv * TR_WAVE + lp) * 8 + 4) = sl_f4{an1[1][0], an1[1][1], an1[1][2], an1[1][3]};
+    for (int jt = 0; jt < 2; ++jt) *reinterpret_cast<wv_f4*>(slice + ((q * 2 + jt) * TR_WAVE + lp) * 4) = gacc[q][jt];
+  *reinterpret_cast<wv_f4*>(sEx + (wv * TR_WAVE + lp) * 8) = wv_f4{an1[0][0], an1[0][1], an1[0][2], an1[0][3]};
+  *reinterpret_cast<wv_f4*>(sEx + (wv * TR_WAVE + lp) * 8 + 4) = wv_f4{an1[1][0], an1[1][1], an1[1][2], an1[1][3]};
   __syncthreads();
   float* sl = slab + (int64_t)blockIdx.x * slab_stride;
   // dPhi0 (A0 and C0 columns): the four pairs' partials in pair order

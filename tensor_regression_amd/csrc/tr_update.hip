@@ -95,7 +95,7 @@ __global__ __launch_bounds__(UPD_T) void k_update(FactorSet fs, int n_bias,
 #pragma unroll
   for (int f = 0; f < TR_MAXF; ++f) {
     if (f < fs.nf) {
-      const float r = tr_wave_allreduce(accn[f]);
+      const float r = wv_allreduce(accn[f]);
       if (lane == 0) wsum[f * 16 + q] = r;
     }
   }
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(64) void k_mttkrp2(FactorSet fs, const float* __res
 #pragma unroll
   for (int r = 0; r < RMAX; ++r) {
     if (r < R) {
-      const float s = tr_wave_allreduce(acc[r]);
+      const float s = wv_allreduce(acc[r]);
       if (lane == r) res = s;
     }
   }

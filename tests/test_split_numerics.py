@@ -1,5 +1,5 @@
 """Numerics of the exact three-term bf16 split the column-slice spectral kernel runs its GEMMs
-with (csrc/tr_spectral_slice.hip: sl_split2 / sl_mfma6 / sl_mfma_lp), restated in numpy on the
+with (bfs_split2 of csrc/tr_bf16_split.h; csrc/tr_spectral_slice.hip: sl_mfma6 / sl_mfma_lp), restated in numpy on the
 fp32 bit patterns (CPU; the kernel itself is covered by tests/test_gpu_spectral.py and, at full
 config-5 size against fp64, tests/test_gpu_fullsize.py).
 

@@ -41,20 +41,12 @@ struct Args {
   int amsgrad;
 };
 
-__device__ __forceinline__ int factor_of(const FactorSet& fs, int64_t e) {
-  int f = 0;
-#pragma unroll
-  for (int g = 1; g < TR_MAXF; ++g)
-    if (g < fs.nf && e >= fs.off[g]) f = g;
-  return f;
-}
-
 __device__ __forceinline__ void norms_finish(const FactorSet& fs, float (&accn)[TR_MAXF], float* wsum, float* norms) {
   const int t = threadIdx.x, lane = t & 63, q = t >> 6, NWV = blockDim.x >> 6;
 #pragma unroll
   for (int f = 0; f < TR_MAXF; ++f)
     if (f < fs.nf) {
-      const float v = tr_wave_allreduce(accn[f]);
+      const float v = wv_allreduce(accn[f]);
       if (lane == 0) wsum[f * 16 + q] = v;
     }
   __syncthreads();
@@ -67,7 +59,7 @@ __device__ __forceinline__ void norms_finish(const FactorSet& fs, float (&accn)[
 }
 
 __device__ __forceinline__ void acc1(const FactorSet& fs, float (&accn)[TR_MAXF], int64_t k, float a) {
-  const int f = factor_of(fs, k);
+  const int f = factor_of(fs, fs.nf, k);
 #pragma unroll
   for (int g = 0; g < TR_MAXF; ++g)
     if (g == f) accn[g] = fmaf(a, a, accn[g]);
@@ -78,7 +70,7 @@ __device__ __forceinline__ void step1(const FactorSet& fs, const Args& ua, const
                                       float* vmax) {
 #pragma clang fp contract(off)
   if (e < fs.nfelem) {
-    const int f = factor_of(fs, e);
+    const int f = factor_of(fs, fs.nf, e);
     g = g + ua.lam / (2.0f * norms[f]) * (2.0f * p);
   }
   mm = fmaf(ua.omb1, g - mm, mm);
@@ -295,14 +287,14 @@ __global__ __launch_bounds__(1024) void v6(FactorSet fs, int nb, float* params, 
   for (int f = 0; f < TR_MAXF; ++f) accn[f] = 0.f;
   for (int64_t k = t; k < fs.nfelem; k += blockDim.x) {
     const float a = params[k];
-    const int f = factor_of(fs, k);
+    const int f = factor_of(fs, fs.nf, k);
 #pragma unroll
     for (int g = 0; g < TR_MAXF; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
   }
 #pragma unroll
   for (int f = 0; f < TR_MAXF; ++f)
     if (f < fs.nf) {
-      const float r = tr_wave_allreduce(accn[f]);
+      const float r = wv_allreduce(accn[f]);
       if (lane == 0) wsum[f * 16 + q] = r;
     }
   __syncthreads();
@@ -318,7 +310,7 @@ __global__ __launch_bounds__(1024) void v6(FactorSet fs, int nb, float* params, 
   for (int64_t e = threadIdx.x; e < np; e += blockDim.x) {
     float g = grad[e], p = params[e], mm = m[e], vv = v[e];
     const float vmo = ua.amsgrad ? vmax[e] : 0.f;
-    const int f = factor_of(fs, e);
+    const int f = factor_of(fs, fs.nf, e);
     g = e < fs.nfelem ? g + coef[f] * (2.0f * p) : g;
     mm = fmaf(ua.omb1, g - mm, mm);
     vv = vv * ua.b2;
@@ -349,7 +341,7 @@ __global__ __launch_bounds__(1024) void v7(FactorSet fs, int nb, float* params, 
   int64_t k = t;
   for (; k + B < fs.nfelem; k += 2 * B) {
     const float a = params[k], b = params[k + B];
-    const int f = factor_of(fs, k), h = factor_of(fs, k + B);
+    const int f = factor_of(fs, fs.nf, k), h = factor_of(fs, fs.nf, k + B);
 #pragma unroll
     for (int g = 0; g < TR_MAXF; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
 #pragma unroll
@@ -357,14 +349,14 @@ __global__ __launch_bounds__(1024) void v7(FactorSet fs, int nb, float* params, 
   }
   if (k < fs.nfelem) {
     const float a = params[k];
-    const int f = factor_of(fs, k);
+    const int f = factor_of(fs, fs.nf, k);
 #pragma unroll
     for (int g = 0; g < TR_MAXF; ++g) accn[g] = g == f ? fmaf(a, a, accn[g]) : accn[g];
   }
 #pragma unroll
   for (int f = 0; f < TR_MAXF; ++f)
     if (f < fs.nf) {
-      const float r = tr_wave_allreduce(accn[f]);
+      const float r = wv_allreduce(accn[f]);
       if (lane == 0) wsum[f * 16 + q] = r;
     }
   __syncthreads();
@@ -378,7 +370,7 @@ __global__ __launch_bounds__(1024) void v7(FactorSet fs, int nb, float* params, 
   if (s0 != 0 || st != 0.f) return;
   const int64_t np = fs.nfelem + nb;
   auto step = [&](int64_t e, float g, float p, float mm, float vv, float vmo) {
-    const int f = factor_of(fs, e);
+    const int f = factor_of(fs, fs.nf, e);
     g = e < fs.nfelem ? g + coef[f] * (2.0f * p) : g;
     mm = fmaf(ua.omb1, g - mm, mm);
     vv = vv * ua.b2;
