@@ -401,6 +401,72 @@ int tr_mnl_score_many(int device, const tr_score_member* members, int n_members,
                       void* table_dev, int64_t table_bytes, void* stream);
 
 /*
+ * Shared-X linear sweep: up to 16 CP linear models with two feature modes (a hyperparameter grid:
+ * one model per grid point) fitted over ONE X (n_rows, I0, I1) float32 at x_row_stride floats
+ * (0 = I0 * I1; a stride below I0 * I1 is a windowed view).  No plan is involved.  With dense
+ * coefficient tensors the members' forward passes are one skinny GEMM over X and their gradient
+ * passes another, so an iteration reads X twice whatever the number of members, and the number of
+ * kernel launches per iteration (8) does not depend on it either.  Members differ in rank,
+ * nonneg[2], softplus settings, weights, target, lambda and every optimizer setting.
+ * The envelope: P = I0 * I1 and the row stride multiples of 4 floats, X 16-byte aligned, rank 1..32,
+ * I0, I1 <= 2^20, P <= 2^30; any n_rows >= 1.
+ * A member's `params` is its plan arena (factor 0, factor 1, bias), `grad` its gradient arena of
+ * (I0 + I1) * rank + 3 floats, laid out as tr_loss_grad leaves it (factor gradients, bias gradient,
+ * data loss, status).  exp_avg / exp_avg_sq / max_exp_avg_sq / loss_hist / stop_flag / step /
+ * hist_base / iter / patience / tol are those of tr_adam_step; n_iters is how many iterations the
+ * call runs for this member (tr_linear_many_step: 0 or 1; tr_linear_many_fit: 0..64).  A member
+ * whose *stop_flag is nonzero or whose n_iters is used up is left untouched: parameters, Adam
+ * state and loss history (its grad arena is scratch).
+ * No floating-point atomics and fixed summation orders that depend on (n_rows, I0, I1) alone: a
+ * member's results are bitwise reproducible and depend neither on the other members nor on its
+ * position in the table.  Given the same gradient bits the update is tr_adam_step's, bit for bit.
+ *   tr_linear_many_envelope        1 inside the envelope, 0 outside; needs no device
+ *   tr_linear_many_workspace_bytes size of the caller's device workspace (<= 0: outside the envelope)
+ *   tr_linear_member_table_bytes   size of the argument table for n_members
+ *   tr_linear_many_loss_grad       one evaluation: fills every member's grad arena
+ *   tr_linear_many_step            the update of every member with n_iters = 1 from its grad arena
+ *   tr_linear_many_fit             max(n_iters) iterations of both
+ * Every entry checks the shape and EVERY member before any device call (NULL buffer, n_iters out of
+ * range, step < 1, iter or hist_base < 0, lr < 0, amsgrad without max_exp_avg_sq, more than 16
+ * members: TR_E_ARG; outside the envelope: TR_E_UNSUPPORTED; tr_last_error() names the member's
+ * index) and launches nothing if one fails.  n_members == 0 succeeds.  table_host (pinned) and
+ * table_dev as in tr_fit_adam_resident_many.
+ */
+typedef struct tr_linear_member {
+  float* params;         /* (I0 + I1) * rank + 1: factor 0, factor 1, bias */
+  const float* weights;  /* [rank] CP component weights */
+  const float* y;        /* [n_rows] targets */
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* max_exp_avg_sq; /* amsgrad only, else may be NULL */
+  float* grad;           /* (I0 + I1) * rank + 3 */
+  double* loss_hist;
+  int32_t* stop_flag;
+  int32_t rank;
+  int32_t nonneg[2];
+  int32_t amsgrad;
+  float softplus_beta, softplus_threshold;
+  float lambda_l2;
+  int32_t n_iters;
+  double lr, beta1, beta2, eps, weight_decay;
+  int64_t step, hist_base, iter, patience;
+  double tol;
+} tr_linear_member;
+
+int tr_linear_many_envelope(int64_t I0, int64_t I1, int64_t x_row_stride, int rank);
+int64_t tr_linear_many_workspace_bytes(int64_t n_rows, int64_t I0, int64_t I1, int n_members);
+int64_t tr_linear_member_table_bytes(int n_members);
+int tr_linear_many_loss_grad(int device, const float* X, int64_t n_rows, int64_t x_row_stride, int64_t I0, int64_t I1,
+                             const tr_linear_member* members, int n_members, void* workspace,
+                             int64_t workspace_bytes, void* table_host, void* table_dev, int64_t table_bytes,
+                             void* stream);
+int tr_linear_many_step(int device, int64_t I0, int64_t I1, const tr_linear_member* members, int n_members,
+                        void* table_host, void* table_dev, int64_t table_bytes, void* stream);
+int tr_linear_many_fit(int device, const float* X, int64_t n_rows, int64_t x_row_stride, int64_t I0, int64_t I1,
+                       const tr_linear_member* members, int n_members, void* workspace, int64_t workspace_bytes,
+                       void* table_host, void* table_dev, int64_t table_bytes, void* stream);
+
+/*
  * Fold the NEXT iteration's factor preparation into tr_adam_step: with enable = 1, on a plan
  * that takes the factored multinomial single pass, every tr_adam_step also computes
  * softplus(A_k) and its derivative from the parameters it has just written, and the following

@@ -12,7 +12,7 @@ from . import multinomial_tensor_regression  # noqa: F401
 from . import multinomial_tensor_regression_hierarchical  # noqa: F401
 from . import spectral_tensor_regression  # noqa: F401
 from . import convolutional_fourier_tensor_regression  # noqa: F401
-from .standard_tensor_regression import CP_linear_regression  # noqa: F401
+from .standard_tensor_regression import CP_linear_regression, fit_Adam_many  # noqa: F401
 from .multinomial_tensor_regression import CP_logistic_regression  # noqa: F401
 
 __version__ = "0.1.0"

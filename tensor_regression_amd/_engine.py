@@ -1341,6 +1341,137 @@ def run_resident_many(dev, members, sync_every=64, trace=None):
     return [int(s) for s in stops], launches
 
 
+LINEAR_MANY_MAX = 16  # members of one group of the shared-X linear sweep (the columns of one MFMA tile)
+
+
+def linear_many_enabled():
+    """TR_LINEAR_MANY=0 sends every model of fit_Adam_many to its own fit_Adam."""
+    return not os.environ.get("TR_LINEAR_MANY", "").startswith("0")
+
+
+def linear_many_envelope(I0, I1, x_row_stride, rank):
+    """tr_linear_many_envelope: whether the shared-X sweep takes this shape (needs no device)."""
+    return bool(_lib.load().tr_linear_many_envelope(int(I0), int(I1), int(x_row_stride), int(rank)))
+
+
+class LinearManyBuffers:
+    """What one group of the shared-X linear sweep needs on the device beside its members' arrays: the
+    workspace of tr_linear_many_workspace_bytes and the two table buffers."""
+
+    def __init__(self, dev, N, I0, I1, M):
+        lib = _lib.load()
+        self.dev, self.M = dev, M
+        self.ws_bytes = int(lib.tr_linear_many_workspace_bytes(N, I0, I1, M))
+        if self.ws_bytes <= 0:
+            raise ValueError(f"the shared-X linear sweep does not take the shape ({N}, {I0}, {I1})")
+        self.table_bytes = max(int(lib.tr_linear_member_table_bytes(M)), 16)
+        with torch.cuda.device(dev):
+            self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=f"cuda:{dev}")
+            self.table_host = torch.empty(self.table_bytes, dtype=torch.uint8, pin_memory=True)
+            self.table_dev = torch.empty(self.table_bytes, dtype=torch.uint8, device=f"cuda:{dev}")
+
+
+def linear_member_array(members):
+    """The (ctypes array, numpy record view of the same memory) of tr_linear_member for `members`:
+    objects with arena, w, y, grad, m, v, vmax | None, hist, stop (device tensors), rank, nonneg[2],
+    beta, thr, lambda_L2, hp, patience, tol, hist_base.  step / iter / n_iters are the caller's."""
+    M = len(members)
+    arr = (_lib.LinearMember * M)()
+    rec = np.frombuffer(arr, dtype=np.dtype(_lib.LinearMember)) if M else None
+    for r, mb in zip(arr, members):
+        r.params, r.weights, r.y, r.grad = mb.arena.data_ptr(), mb.w.data_ptr(), mb.y.data_ptr(), mb.grad.data_ptr()
+        r.exp_avg, r.exp_avg_sq = mb.m.data_ptr(), mb.v.data_ptr()
+        r.max_exp_avg_sq = mb.vmax.data_ptr() if mb.vmax is not None else None
+        r.loss_hist, r.stop_flag = mb.hist.data_ptr(), mb.stop.data_ptr()
+        r.rank = int(mb.rank)
+        r.nonneg[0], r.nonneg[1] = (1 if mb.nonneg[0] else 0), (1 if mb.nonneg[1] else 0)
+        r.amsgrad = 1 if mb.hp["amsgrad"] else 0
+        r.softplus_beta, r.softplus_threshold, r.lambda_l2 = float(mb.beta), float(mb.thr), float(mb.lambda_L2)
+        r.lr, r.beta1, r.beta2, r.eps, r.weight_decay = (mb.hp[k] for k in ("lr", "beta1", "beta2", "eps",
+                                                                            "weight_decay"))
+        r.hist_base, r.patience, r.tol = int(mb.hist_base), int(mb.patience), float(mb.tol)
+        r.step, r.iter, r.n_iters = 1, 0, 0
+    return arr, rec
+
+
+def run_linear_many(dev, X, members, sync_every=64, trace=None):
+    """Fit up to 16 two-mode CP linear models over one X together (tr_linear_many_fit): every chunk of
+    up to `sync_every` (<= 64) iterations is one call, 8 kernel launches per iteration whatever the
+    number of members, X read twice per iteration.
+
+    X: (N, I0, I1) float32 on cuda:`dev`, samples contiguous, any row stride inside the envelope.
+    `members`: objects with arena (factor 0, factor 1, bias; float32 on the device), w [R], y [N],
+    rank, nonneg[2], beta, thr (softplus), lambda_L2, hp (adam_hparams), max_iter, tol, patience and
+    loss_running (extended in place).  All members start at loop index 0 and advance together; a member
+    past its own max_iter or stopped on its plateau is left untouched from then on.  One host sync per
+    chunk: the copy of the int32[M] stop array.  Returns (stop values, X passes): stop > 0 is a plateau
+    after that many iterations.  `trace` (a list, for tools/linear_many_shapes.py) receives per chunk
+    (iterations, ms between device events around the call)."""
+    lib = _lib.load()
+    M = len(members)
+    if M == 0:
+        return [], 0
+    if M > LINEAR_MANY_MAX:
+        raise ValueError(f"run_linear_many takes at most {LINEAR_MANY_MAX} members, got {M}")
+    device = f"cuda:{dev}"
+    N, I0, I1 = (int(d) for d in X.shape)
+    xld = int(X.stride(0)) if N > 1 else I0 * I1
+    seg = lambda n: -(-n // 64) * 64  # 256-byte aligned segments
+    state_at, hist_at, ns, nh = [], [], 0, 0
+    for mb in members:
+        state_at.append(ns)
+        ns += 4 * seg(mb.arena.numel() + 2)
+        hist_at.append(nh)
+        nh += seg(len(mb.loss_running) + max(int(mb.max_iter), 0) + 1)
+    hist_host = np.zeros(nh, dtype=np.float64)
+    for mb, at in zip(members, hist_at):  # the plateau test reads the earlier losses
+        if mb.loss_running:
+            hist_host[at:at + len(mb.loss_running)] = mb.loss_running
+    bufs = LinearManyBuffers(dev, N, I0, I1, M)
+    with torch.cuda.device(dev):
+        state = torch.zeros(ns, dtype=torch.float32, device=device)
+        hist = torch.from_numpy(hist_host).to(device)
+        stop = torch.zeros(M, dtype=torch.int32, device=device)
+    for j, mb in enumerate(members):
+        n, s0 = mb.arena.numel(), state_at[j]
+        mb.grad, mb.m, mb.v = state[s0:s0 + n + 2], state[s0 + seg(n + 2):][:n], state[s0 + 2 * seg(n + 2):][:n]
+        mb.vmax = state[s0 + 3 * seg(n + 2):][:n] if mb.hp["amsgrad"] else None
+        mb.hist, mb.stop, mb.hist_base = hist[hist_at[j]:], stop[j:], len(mb.loss_running)
+    arr, rec = linear_member_array(members)
+    max_iters = np.array([max(int(mb.max_iter), 0) for mb in members], dtype=np.int64)
+    stops = np.zeros(M, dtype=np.int32)
+    ii, passes = 0, 0
+    stream = stream_handle(dev)
+    while True:
+        left = np.where(stops == 0, max_iters - ii, 0)
+        if not (left > 0).any():
+            break
+        n = min(int(sync_every), int(left.max()))
+        rec["n_iters"] = np.clip(left, 0, n)
+        rec["step"] = ii + 1
+        rec["iter"] = ii
+        with torch.cuda.device(dev):
+            if trace is not None:
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev[0].record()
+            check(lib.tr_linear_many_fit(dev, ptr(X), N, xld, I0, I1, arr, M, ptr(bufs.ws), bufs.ws_bytes,
+                                         ptr(bufs.table_host), ptr(bufs.table_dev), bufs.table_bytes, stream),
+                  "tr_linear_many_fit")
+            passes += 2 * n
+            if trace is not None:
+                ev[1].record()
+            stops = stop.cpu().numpy()  # the one host sync of the chunk (table_host is free again after it)
+            if trace is not None:
+                trace.append((n, ev[0].elapsed_time(ev[1])))
+        ii += n
+    hist_host = hist.cpu().numpy()
+    for j, mb in enumerate(members):
+        n_run = abs(int(stops[j])) if stops[j] else int(max_iters[j])
+        base = hist_at[j] + len(mb.loss_running)
+        mb.loss_running.extend(hist_host[base:base + n_run].tolist())
+    return [int(s) for s in stops], passes
+
+
 SCORE_ROW_BLOCK = _lib.TR_SCORE_ROW_BLOCK  # rows per workgroup of tr_mnl_score_many
 
 

@@ -15,6 +15,8 @@ Differences from the reference (all deliberate):
   * a 2-D `y` is rejected (the reference silently broadcasts (N,) - (N,1) to (N,N), quirk Q11);
   * `fit_Adam` takes an optional `process_group` to fit sample shards over torch.distributed.
 """
+import types
+
 import numpy as np
 import torch
 
@@ -22,7 +24,7 @@ from . import _engine, _lib
 from ._engine import Plan, as_device_f32, adam_hparams, run_adam_fit
 
 __all__ = ["make_BcpInit", "non_neg_fn", "lin_model", "stepwise_model", "L2_penalty",
-           "CP_linear_regression"]
+           "CP_linear_regression", "fit_Adam_many"]
 
 
 ####################################
@@ -386,3 +388,165 @@ class CP_linear_regression():
             axs[ii].set_title(f'factor {ii}')
             axs[ii].plot(val)
         fig.suptitle('components')
+
+
+####################################
+####### Many models, one X #########
+####################################
+
+# Groups of fewer models go to the models' own fit_Adam: the single-pass kernel reads X once per
+# iteration and a group reads it twice, so a small group cannot win.  Measured (tools/
+# linear_many_shapes.py, DESIGN.md "Shared-X linear sweep"): a group of 2 loses (0.86x the loop), 4 is
+# the smallest measured size that wins at both shapes (1.66x and 1.68x).
+LINEAR_MANY_MIN_BATCH = 4
+
+
+def _per_member(name, value, M):
+    """One value for all M models, or a list of M values (ValueError on another length)."""
+    if not isinstance(value, (list, tuple)):
+        return [value] * M
+    if len(value) != M:
+        raise ValueError(f"{name}: a list must hold one value per model ({M}), got {len(value)}")
+    return list(value)
+
+
+def _targets(y, M):
+    """y as M targets: one (N,) target for all models, or a list of M of them."""
+    if isinstance(y, (list, tuple)) and len(y) > 0 and all(hasattr(e, "__len__") for e in y):
+        if len(y) != M:
+            raise ValueError(f"y: a list must hold one target per model ({M}), got {len(y)}")
+        return list(y), False
+    return [y] * M, True
+
+
+def fit_Adam_many(models, X, y, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, verbose=False,
+                  Adam_kwargs=None, min_batch=None, report=None):
+    """fit_Adam of many CP_linear_regression models over ONE X: the outer loop of a hyperparameter grid
+    (demo_TensorRegression.ipynb: a fresh model per value of lambda_L2, every fit on the same X and y)
+    with X streamed twice per iteration for a whole group of models instead of once per model.
+
+    models: CP_linear_regression objects of this module, each with its own rank, non_negative,
+    softplus_kwargs, weights, initial Bcp and bias; the feature dims of each must equal X.shape[1:].
+    X: one device tensor for all models (a strided or util.windowed_view X is allowed).  y: one (N,)
+    target for all models or a list of len(models) targets.  lambda_L2, max_iter, tol, patience and
+    Adam_kwargs are each one value for all models or a list of len(models) values.  Afterwards every
+    model is in the state its own `model.fit_Adam(X, y, ...)` would have left it, up to fp32 summation
+    order (Bcp, bias, loss_running extended, plateau stops included); `model._plan` is untouched.  The
+    returned list holds each model's convergence_reached.
+
+    A model inside the envelope is fitted in a group: float32, two feature modes (3-D X), rank <= 32,
+    P = I * J and X's row stride multiples of 4 floats (a stride below P, a windowed view, included),
+    any N >= 1.  Groups hold up to 16 models in list order and run one after another; a group of fewer
+    than `min_batch` models (None: LINEAR_MANY_MIN_BATCH) and every model outside the envelope go to
+    their own fit_Adam, as does every model when X is a util.HostStream, the dtype is float64 or
+    TR_LINEAR_MANY=0.  report (a dict) receives {'batched': indices, 'alone': indices, 'groups': n,
+    'x_passes': n} (x_passes: passes over X made by the groups).  verbose=2 (a line per iteration) is
+    not offered, and neither is process_group."""
+    from .util import HostStream
+    models = list(models)
+    M = len(models)
+    if verbose == 2:
+        raise NotImplementedError("fit_Adam_many: verbose=2 prints every iteration of every model; call fit_Adam "
+                                  "on each model instead")
+    given = dict(lambda_L2=lambda_L2, max_iter=max_iter, tol=tol, patience=patience, Adam_kwargs=Adam_kwargs)
+    args = {k: _per_member(k, v, M) for k, v in given.items()}
+    ys, shared_y = _targets(y, M)
+    if len({id(m) for m in models}) != M:
+        raise ValueError("fit_Adam_many: the same model object appears twice")
+    for m in models:
+        if not isinstance(m, CP_linear_regression):
+            raise TypeError(f"fit_Adam_many takes this module's CP_linear_regression objects, got {type(m).__name__}")
+    if min_batch is None:
+        min_batch = LINEAR_MANY_MIN_BATCH
+    if int(min_batch) < 1:
+        raise ValueError(f"min_batch must be >= 1, got {min_batch}")
+    if report is not None:
+        report.clear()
+        report.update(batched=[], alone=[], groups=0, x_passes=0)
+    if M == 0:
+        return []
+    hps = [adam_hparams(ak) for ak in args["Adam_kwargs"]]  # TypeError on None, as fit_Adam
+    if not isinstance(X, (torch.Tensor, HostStream)):
+        raise TypeError(f"fit_Adam_many: X must be a torch tensor or a util.HostStream, got {type(X).__name__}")
+    N = len(X) if isinstance(X, HostStream) else int(X.shape[0])
+    for j, m in enumerate(models):
+        m._check_dtype()
+        dims = [int(A.shape[0]) for A in m.Bcp]
+        if list(X.shape[1:]) != dims:
+            raise ValueError(f"model {j}: Incorrect shapes for inner product along {len(dims)} common modes. "
+                             f"tensor_1.shape={list(X.shape)}, factors={[tuple(A.shape) for A in m.Bcp]}")
+    for j, yj in enumerate(ys[:1] if shared_y else ys):
+        shp = tuple(torch.as_tensor(yj).shape) if not isinstance(yj, torch.Tensor) else tuple(yj.shape)
+        if len(shp) != 1 or shp[0] != N:
+            raise ValueError(f"y{'' if shared_y else f'[{j}]'} must be 1-D with len(y) == X.shape[0]; got "
+                             f"y.shape={shp}, X.shape[0]={N}")
+    # ---- routing ----
+    inside = []
+    grouped = (_engine.linear_many_enabled() and isinstance(X, torch.Tensor) and X.dtype == torch.float32
+               and X.ndim == 3)
+    if grouped:
+        dev = _engine.compute_device(X, models[0].device)
+        X = _engine.as_device_rows(X, dev, torch.float32)
+        I0, I1 = int(X.shape[1]), int(X.shape[2])
+        xld = int(X.stride(0)) if N > 1 else I0 * I1
+        inside = [j for j, m in enumerate(models)
+                  if m.dtype == torch.float32 and len(m.Bcp) == 2
+                  and _engine.linear_many_envelope(I0, I1, xld, int(m.Bcp[0].shape[1]))]
+    groups = [inside[k:k + _engine.LINEAR_MANY_MAX] for k in range(0, len(inside), _engine.LINEAR_MANY_MAX)]
+    groups = [g for g in groups if len(g) >= int(min_batch)]
+    batched = [j for g in groups for j in g]
+    alone = [j for j in range(M) if j not in set(batched)]
+    results = [False] * M
+    passes = 0
+    y_dev = {}
+
+    def target(j):  # a shared y is uploaded once
+        key = 0 if shared_y else j
+        if key not in y_dev:
+            y_dev[key] = as_device_f32(torch.as_tensor(ys[j]), dev, torch.float32)
+        return y_dev[key]
+
+    for g in groups:
+        members, srcs, offsets, total = [], [], [], 0
+        for j in g:
+            m = models[j]
+            R = int(m.Bcp[0].shape[1])
+            nn, beta, thr = _engine.nonlin_key(m.non_negative, m.softplus_kwargs, 2)
+            for f, A in enumerate(m.Bcp):
+                A = torch.as_tensor(A)
+                if tuple(A.shape) != ((I0, I1)[f], R):
+                    raise ValueError(f"model {j}: factor {f} has shape {tuple(A.shape)}, expected {((I0, I1)[f], R)}")
+                srcs.append(A.detach().reshape(-1))
+                offsets.append(total)
+                total += A.numel()
+            srcs.append(torch.as_tensor(m.bias).detach().reshape(-1)[:1])
+            offsets.append(total)
+            total += 1
+            w = torch.as_tensor(m.weights).to(f"cuda:{dev}", torch.float32).contiguous()
+            if w.numel() != R:
+                raise ValueError(f"model {j}: weights holds {w.numel()} values, the rank is {R}")
+            members.append(types.SimpleNamespace(
+                y=target(j), w=w, rank=R, nonneg=nn, beta=beta, thr=thr, lambda_L2=args["lambda_L2"][j], hp=hps[j],
+                max_iter=args["max_iter"][j], tol=args["tol"][j], patience=args["patience"][j],
+                loss_running=m.loss_running))
+        # every member's parameters in ONE arena (one launch to pack, one to write back), a slice each
+        arena = _engine._pack_arena(srcs, total, torch.float32, f"cuda:{dev}")
+        bounds = offsets + [total]
+        for k, mb in enumerate(members):
+            mb.arena = arena[bounds[3 * k]:bounds[3 * k + 3]]
+        stops, n_pass = _engine.run_linear_many(dev, X, members)
+        passes += n_pass
+        _engine._unpack_arena(arena, offsets, [t for j in g for t in (*models[j].Bcp, models[j].bias)])
+        for j, s in zip(g, stops):
+            results[j] = s > 0
+    for j in alone:  # outside the envelope, a small group or the route switched off: the model's own fit
+        results[j] = models[j].fit_Adam(X, ys[j], lambda_L2=args["lambda_L2"][j], max_iter=args["max_iter"][j],
+                                        tol=args["tol"][j], patience=args["patience"][j], verbose=False,
+                                        Adam_kwargs=args["Adam_kwargs"][j])
+    if (verbose is True) or (verbose >= 1):
+        for j, conv in enumerate(results):
+            print(f"model {j}: " + ('Convergence reached' if conv else
+                                    'Reached maximum number of iterations without convergence'))
+    if report is not None:
+        report.update(batched=batched, alone=alone, groups=len(groups), x_passes=passes)
+    return results
