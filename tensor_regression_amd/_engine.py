@@ -1233,6 +1233,109 @@ def run_adam_fit_groups(plan, X, target, class_weight, norm, arena, weights, lam
                       one_launch if resident else streamed)
 
 
+_TABLES = {}  # device index -> (pinned host table, device table) of the many-model routes
+
+
+def table_buffers(dev, nbytes):
+    """The (pinned host, device) uint8 buffers of at least `nbytes` in which a many-model call builds its member
+    table and to which it uploads it.  One pair per device, grown on demand and shared by every route:
+    pinning memory costs more than a small call.  Every use ends in a host sync after its last upload
+    (the stop array's or the results' copy to the host), so the next call, of any route, finds it free."""
+    held = _TABLES.get(dev)
+    if held is None or held[0].numel() < nbytes:
+        with torch.cuda.device(dev):
+            held = _TABLES[dev] = (torch.empty(nbytes, dtype=torch.uint8, pin_memory=True),
+                                   torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{dev}"))
+    return held
+
+
+def member_records(ctype, M):
+    """(ctypes array of M `ctype` members, numpy record view of the same memory: a field is a column)."""
+    arr = (ctype * M)()
+    return arr, (np.frombuffer(arr, dtype=np.dtype(ctype)) if M else None)
+
+
+def fill_adam_fields(r, mb, hist_base):
+    """The fields that tr_resident_member and tr_linear_member share, from a member object's own."""
+    for f in range(len(r.nonneg)):
+        r.nonneg[f] = 1 if mb.nonneg[f] else 0
+    r.amsgrad = 1 if mb.hp["amsgrad"] else 0
+    r.softplus_beta, r.softplus_threshold, r.lambda_l2 = float(mb.beta), float(mb.thr), float(mb.lambda_L2)
+    r.beta1, r.beta2, r.eps, r.weight_decay = (mb.hp[k] for k in ("beta1", "beta2", "eps", "weight_decay"))
+    r.hist_base, r.patience, r.tol = int(hist_base), int(mb.patience), float(mb.tol)
+
+
+def next_chunk(stops, max_iters, ii, sync_every, breaks):
+    """The next chunk of a many-model fit at loop index ii: (n, n_iters per member), or None when every
+    member is done (stopped on its plateau, stops != 0, or past its own max_iters).  n is at most
+    sync_every and never crosses one of `breaks`; a member runs min(n, what it has left) iterations."""
+    left = np.where(stops == 0, max_iters - ii, 0)
+    if not (left > 0).any():
+        return None
+    n = min([int(sync_every), int(left.max())] + [b - ii for b in breaks if b > ii])
+    return n, np.clip(left, 0, n)
+
+
+def _run_many_fit(dev, members, rec, state_fields, state_len, call, breaks, sync_every, on_chunk):
+    """The chunked loop of run_resident_many and run_linear_many.  All members start at loop index 0 and
+    advance together, a chunk (next_chunk) per `call(ii)`, the route's C call; one host sync per chunk:
+    the copy of the int32[M] stop array.  Extends every loss_running; returns (stop values, chunk sizes).
+    Filled in `rec`, the record view of the members' ctypes array: `state_fields`, its pointers into ONE
+    zeroed float32 buffer, a 256-byte aligned segment of state_len(member) floats each (max_exp_avg_sq
+    NULL without amsgrad); loss_hist, into one fp64 buffer seeded with the earlier losses; stop_flag; per
+    chunk n_iters, step and iter.  `on_chunk(n, device ms of the call, wall ms of the chunk)`, or None,
+    runs after the sync."""
+    M = len(members)
+    device = f"cuda:{dev}"
+    seg = lambda n: -(-n // 64) * 64  # 256-byte aligned segments
+    segs = np.array([seg(state_len(mb)) for mb in members], dtype=np.int64)
+    hists = np.array([seg(len(mb.loss_running) + max(int(mb.max_iter), 0) + 1) for mb in members], dtype=np.int64)
+    state_at = np.cumsum(len(state_fields) * segs) - len(state_fields) * segs
+    hist_at = np.cumsum(hists) - hists
+    hist_host = np.zeros(int(hists.sum()), dtype=np.float64)
+    for mb, at in zip(members, hist_at):  # the plateau test reads the earlier losses
+        if mb.loss_running:
+            hist_host[at:at + len(mb.loss_running)] = mb.loss_running
+    with torch.cuda.device(dev):
+        state = torch.zeros(int(len(state_fields) * segs.sum()), dtype=torch.float32, device=device)
+        hist = torch.from_numpy(hist_host).to(device)
+        stop = torch.zeros(M, dtype=torch.int32, device=device)
+    for k, name in enumerate(state_fields):
+        rec[name] = state.data_ptr() + 4 * (state_at + k * segs)
+    rec["max_exp_avg_sq"] = np.where([bool(mb.hp["amsgrad"]) for mb in members], rec["max_exp_avg_sq"], 0)
+    rec["loss_hist"] = hist.data_ptr() + 8 * hist_at
+    rec["stop_flag"] = stop.data_ptr() + 4 * np.arange(M)
+    max_iters = np.array([max(int(mb.max_iter), 0) for mb in members], dtype=np.int64)
+    stops = np.zeros(M, dtype=np.int32)
+    ii, chunks, t_chunk = 0, [], time.perf_counter()
+    while True:
+        chunk = next_chunk(stops, max_iters, ii, sync_every, breaks)
+        if chunk is None:
+            break
+        n, rec["n_iters"] = chunk
+        rec["step"] = ii + 1
+        rec["iter"] = ii
+        with torch.cuda.device(dev):
+            if on_chunk is not None:
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev[0].record()
+            call(ii)
+            if on_chunk is not None:
+                ev[1].record()
+            stops = stop.cpu().numpy()  # the one host sync of the chunk (the table pair is free again after it)
+            if on_chunk is not None:
+                t_chunk, was = time.perf_counter(), t_chunk
+                on_chunk(n, ev[0].elapsed_time(ev[1]), (t_chunk - was) * 1e3)
+        chunks.append(n)
+        ii += n
+    hist_host = hist.cpu().numpy()
+    for j, mb in enumerate(members):
+        n_run = abs(int(stops[j])) if stops[j] else int(max_iters[j])
+        base = hist_at[j] + len(mb.loss_running)
+        mb.loss_running.extend(hist_host[base:base + n_run].tolist())
+    return [int(s) for s in stops], chunks
+
+
 def resident_max_rows(I0, I1, n_classes, rank):
     """tr_mnl_resident_max_rows: the largest sample count the resident fit holds for this shape (0: none)."""
     return int(_lib.load().tr_mnl_resident_max_rows(int(I0), int(I1), int(n_classes), int(rank)))
@@ -1250,95 +1353,36 @@ def run_resident_many(dev, members, sync_every=64, trace=None):
     `members`: objects with X (N, I0, I1) float32 and y int64 on cuda:`dev`, arena (the three factors,
     packed), w [R], n_classes, rank, nonneg[3], beta, thr (softplus), lambda_L2, hp (adam_hparams),
     lr_at(ii) -> three learning rates, breaks (loop indices where a learning rate changes), max_iter,
-    tol, patience and loss_running (extended in place, as run_adam_fit_groups does).  All members start
-    at loop index 0 and advance together; a chunk is cut at the union of the members' breaks (lr is
-    constant per launch, and cutting never changes the bits); a member past its own max_iter or
-    stopped on its plateau gets n_iters = 0 from then on.  One host sync per chunk: the copy of the
-    int32[M] stop array.  Returns (stop values, launches): stop > 0 is a plateau after that many
-    iterations.  `trace` (a list, for tools/hier_many_shapes.py) receives per launch (iterations,
+    tol, patience and loss_running (extended in place, as run_adam_fit_groups does).  The loop is
+    _run_many_fit's; a chunk is cut at the union of the members' breaks (lr is constant per launch, and
+    cutting never changes the bits).  Returns (stop values, launches): stop > 0 is a plateau after that
+    many iterations.  `trace` (a list, for tools/hier_many_shapes.py) receives per launch (iterations,
     ms between device events around the table upload and the kernel, ms of wall time of the chunk)."""
     lib = _lib.load()
     M = len(members)
-    device = f"cuda:{dev}"
-    seg = lambda n: -(-n // 64) * 64  # 256-byte aligned segments
-    # one zeroed buffer for every member's Adam state, one for the loss histories, one stop array
-    state_at, hist_at, ns, nh = [], [], 0, 0
-    for mb in members:
-        P = mb.arena.numel()
-        state_at.append(ns)
-        ns += 3 * seg(P)
-        hist_at.append(nh)
-        nh += seg(len(mb.loss_running) + max(int(mb.max_iter), 0) + 1)
-    hist_host = np.zeros(nh, dtype=np.float64)
-    for mb, at in zip(members, hist_at):  # the plateau test reads the earlier losses
-        if mb.loss_running:
-            hist_host[at:at + len(mb.loss_running)] = mb.loss_running
-    with torch.cuda.device(dev):
-        state = torch.zeros(ns, dtype=torch.float32, device=device)
-        hist = torch.from_numpy(hist_host).to(device)
-        stop = torch.zeros(M, dtype=torch.int32, device=device)
-        nbytes = int(lib.tr_resident_member_table_bytes(M))
-        table_host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-        table_dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    arr = (_lib.ResidentMember * M)()
-    rec = np.frombuffer(arr, dtype=np.dtype(_lib.ResidentMember))  # the same memory, column-wise
-    for j, mb in enumerate(members):
-        r, P = arr[j], mb.arena.numel()
+    nbytes = int(lib.tr_resident_member_table_bytes(M))
+    table_host, table_dev = table_buffers(dev, nbytes)
+    arr, rec = member_records(_lib.ResidentMember, M)
+    for r, mb in zip(arr, members):
         N, I0, I1 = (int(d) for d in mb.X.shape)
-        s0 = state_at[j]
         r.X, r.target, r.params, r.weights = mb.X.data_ptr(), mb.y.data_ptr(), mb.arena.data_ptr(), mb.w.data_ptr()
-        r.exp_avg = state[s0:].data_ptr()
-        r.exp_avg_sq = state[s0 + seg(P):].data_ptr()
-        r.max_exp_avg_sq = state[s0 + 2 * seg(P):].data_ptr() if mb.hp["amsgrad"] else None
-        r.loss_hist = hist[hist_at[j]:].data_ptr()
-        r.stop_flag = stop[j:].data_ptr()
         r.n_rows, r.I0, r.I1, r.n_classes, r.rank = N, I0, I1, int(mb.n_classes), int(mb.rank)
         r.x_row_stride = int(mb.X.stride(0)) if N > 1 else I0 * I1
-        for f in range(3):
-            r.nonneg[f] = 1 if mb.nonneg[f] else 0
-        r.amsgrad = 1 if mb.hp["amsgrad"] else 0
-        r.softplus_beta, r.softplus_threshold, r.lambda_l2 = float(mb.beta), float(mb.thr), float(mb.lambda_L2)
-        r.beta1, r.beta2, r.eps, r.weight_decay = (mb.hp[k] for k in ("beta1", "beta2", "eps", "weight_decay"))
-        r.hist_base, r.patience, r.tol = len(mb.loss_running), int(mb.patience), float(mb.tol)
-    max_iters = np.array([max(int(mb.max_iter), 0) for mb in members], dtype=np.int64)
-    breaks = sorted({int(b) for mb in members for b in mb.breaks})
+        fill_adam_fields(r, mb, len(mb.loss_running))
     lrs_const = all(not mb.breaks for mb in members)
-    stops = np.zeros(M, dtype=np.int32)
-    ii, launches, first = 0, 0, True
     stream = stream_handle(dev)
-    t_chunk = time.perf_counter()
-    while True:
-        left = np.where(stops == 0, max_iters - ii, 0)
-        if not (left > 0).any():
-            break
-        n = min([int(sync_every), int(left.max())] + [b - ii for b in breaks if b > ii])
-        rec["n_iters"] = np.clip(left, 0, n)
-        rec["step"] = ii + 1
-        rec["iter"] = ii
-        if first or not lrs_const:
+
+    def call(ii):  # lr is constant per launch: the chunks are cut at the breaks
+        if ii == 0 or not lrs_const:
             rec["lr"] = np.array([mb.lr_at(ii)[:3] for mb in members], dtype=np.float64).reshape(M, 3)
-        first = False
-        with torch.cuda.device(dev):
-            if trace is not None:
-                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-                ev[0].record()
-            check(lib.tr_fit_adam_resident_many(dev, arr, M, ptr(table_host), ptr(table_dev), nbytes, stream),
-                  "tr_fit_adam_resident_many")
-            launches += 1
-            if trace is not None:
-                ev[1].record()
-            stops = stop.cpu().numpy()  # the one host sync of the chunk (table_host is free again after it)
-            if trace is not None:
-                now = time.perf_counter()
-                trace.append((n, ev[0].elapsed_time(ev[1]), (now - t_chunk) * 1e3))
-                t_chunk = now
-        ii += n
-    hist_host = hist.cpu().numpy()
-    for j, mb in enumerate(members):
-        n_run = abs(int(stops[j])) if stops[j] else int(max_iters[j])
-        base = hist_at[j] + len(mb.loss_running)
-        mb.loss_running.extend(hist_host[base:base + n_run].tolist())
-    return [int(s) for s in stops], launches
+        check(lib.tr_fit_adam_resident_many(dev, arr, M, ptr(table_host), ptr(table_dev), nbytes, stream),
+              "tr_fit_adam_resident_many")
+
+    stops, chunks = _run_many_fit(dev, members, rec, ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"),
+                                  lambda mb: mb.arena.numel(), call,
+                                  sorted({int(b) for mb in members for b in mb.breaks}), sync_every,
+                                  None if trace is None else lambda *t: trace.append(t))
+    return stops, len(chunks)
 
 
 LINEAR_MANY_MAX = 16  # members of one group of the shared-X linear sweep (the columns of one MFMA tile)
@@ -1367,30 +1411,24 @@ class LinearManyBuffers:
         self.table_bytes = max(int(lib.tr_linear_member_table_bytes(M)), 16)
         with torch.cuda.device(dev):
             self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=f"cuda:{dev}")
-            self.table_host = torch.empty(self.table_bytes, dtype=torch.uint8, pin_memory=True)
-            self.table_dev = torch.empty(self.table_bytes, dtype=torch.uint8, device=f"cuda:{dev}")
+        self.table_host, self.table_dev = table_buffers(dev, self.table_bytes)
 
 
-def linear_member_array(members):
+def linear_member_array(members, own_state=True):
     """The (ctypes array, numpy record view of the same memory) of tr_linear_member for `members`:
     objects with arena, w, y, grad, m, v, vmax | None, hist, stop (device tensors), rank, nonneg[2],
-    beta, thr, lambda_L2, hp, patience, tol, hist_base.  step / iter / n_iters are the caller's."""
-    M = len(members)
-    arr = (_lib.LinearMember * M)()
-    rec = np.frombuffer(arr, dtype=np.dtype(_lib.LinearMember)) if M else None
+    beta, thr, lambda_L2, hp, patience, tol, hist_base.  step / iter / n_iters are the caller's.
+    own_state=False: the members bring no grad, m, v, vmax, hist, stop and hist_base (_run_many_fit's)."""
+    arr, rec = member_records(_lib.LinearMember, len(members))
     for r, mb in zip(arr, members):
-        r.params, r.weights, r.y, r.grad = mb.arena.data_ptr(), mb.w.data_ptr(), mb.y.data_ptr(), mb.grad.data_ptr()
-        r.exp_avg, r.exp_avg_sq = mb.m.data_ptr(), mb.v.data_ptr()
-        r.max_exp_avg_sq = mb.vmax.data_ptr() if mb.vmax is not None else None
-        r.loss_hist, r.stop_flag = mb.hist.data_ptr(), mb.stop.data_ptr()
-        r.rank = int(mb.rank)
-        r.nonneg[0], r.nonneg[1] = (1 if mb.nonneg[0] else 0), (1 if mb.nonneg[1] else 0)
-        r.amsgrad = 1 if mb.hp["amsgrad"] else 0
-        r.softplus_beta, r.softplus_threshold, r.lambda_l2 = float(mb.beta), float(mb.thr), float(mb.lambda_L2)
-        r.lr, r.beta1, r.beta2, r.eps, r.weight_decay = (mb.hp[k] for k in ("lr", "beta1", "beta2", "eps",
-                                                                            "weight_decay"))
-        r.hist_base, r.patience, r.tol = int(mb.hist_base), int(mb.patience), float(mb.tol)
+        r.params, r.weights, r.y = mb.arena.data_ptr(), mb.w.data_ptr(), mb.y.data_ptr()
+        r.rank, r.lr = int(mb.rank), mb.hp["lr"]
+        fill_adam_fields(r, mb, mb.hist_base if own_state else len(mb.loss_running))
         r.step, r.iter, r.n_iters = 1, 0, 0
+        if own_state:
+            r.grad, r.exp_avg, r.exp_avg_sq = mb.grad.data_ptr(), mb.m.data_ptr(), mb.v.data_ptr()
+            r.max_exp_avg_sq = mb.vmax.data_ptr() if mb.vmax is not None else None
+            r.loss_hist, r.stop_flag = mb.hist.data_ptr(), mb.stop.data_ptr()
     return arr, rec
 
 
@@ -1402,74 +1440,31 @@ def run_linear_many(dev, X, members, sync_every=64, trace=None):
     X: (N, I0, I1) float32 on cuda:`dev`, samples contiguous, any row stride inside the envelope.
     `members`: objects with arena (factor 0, factor 1, bias; float32 on the device), w [R], y [N],
     rank, nonneg[2], beta, thr (softplus), lambda_L2, hp (adam_hparams), max_iter, tol, patience and
-    loss_running (extended in place).  All members start at loop index 0 and advance together; a member
-    past its own max_iter or stopped on its plateau is left untouched from then on.  One host sync per
-    chunk: the copy of the int32[M] stop array.  Returns (stop values, X passes): stop > 0 is a plateau
-    after that many iterations.  `trace` (a list, for tools/linear_many_shapes.py) receives per chunk
-    (iterations, ms between device events around the call)."""
+    loss_running (extended in place).  The loop is _run_many_fit's.  Returns (stop values, X passes):
+    stop > 0 is a plateau after that many iterations.  `trace` (a list, for tools/linear_many_shapes.py)
+    receives per chunk (iterations, ms between device events around the call)."""
     lib = _lib.load()
     M = len(members)
     if M == 0:
         return [], 0
     if M > LINEAR_MANY_MAX:
         raise ValueError(f"run_linear_many takes at most {LINEAR_MANY_MAX} members, got {M}")
-    device = f"cuda:{dev}"
     N, I0, I1 = (int(d) for d in X.shape)
     xld = int(X.stride(0)) if N > 1 else I0 * I1
-    seg = lambda n: -(-n // 64) * 64  # 256-byte aligned segments
-    state_at, hist_at, ns, nh = [], [], 0, 0
-    for mb in members:
-        state_at.append(ns)
-        ns += 4 * seg(mb.arena.numel() + 2)
-        hist_at.append(nh)
-        nh += seg(len(mb.loss_running) + max(int(mb.max_iter), 0) + 1)
-    hist_host = np.zeros(nh, dtype=np.float64)
-    for mb, at in zip(members, hist_at):  # the plateau test reads the earlier losses
-        if mb.loss_running:
-            hist_host[at:at + len(mb.loss_running)] = mb.loss_running
     bufs = LinearManyBuffers(dev, N, I0, I1, M)
-    with torch.cuda.device(dev):
-        state = torch.zeros(ns, dtype=torch.float32, device=device)
-        hist = torch.from_numpy(hist_host).to(device)
-        stop = torch.zeros(M, dtype=torch.int32, device=device)
-    for j, mb in enumerate(members):
-        n, s0 = mb.arena.numel(), state_at[j]
-        mb.grad, mb.m, mb.v = state[s0:s0 + n + 2], state[s0 + seg(n + 2):][:n], state[s0 + 2 * seg(n + 2):][:n]
-        mb.vmax = state[s0 + 3 * seg(n + 2):][:n] if mb.hp["amsgrad"] else None
-        mb.hist, mb.stop, mb.hist_base = hist[hist_at[j]:], stop[j:], len(mb.loss_running)
-    arr, rec = linear_member_array(members)
-    max_iters = np.array([max(int(mb.max_iter), 0) for mb in members], dtype=np.int64)
-    stops = np.zeros(M, dtype=np.int32)
-    ii, passes = 0, 0
+    arr, rec = linear_member_array(members, own_state=False)
     stream = stream_handle(dev)
-    while True:
-        left = np.where(stops == 0, max_iters - ii, 0)
-        if not (left > 0).any():
-            break
-        n = min(int(sync_every), int(left.max()))
-        rec["n_iters"] = np.clip(left, 0, n)
-        rec["step"] = ii + 1
-        rec["iter"] = ii
-        with torch.cuda.device(dev):
-            if trace is not None:
-                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-                ev[0].record()
-            check(lib.tr_linear_many_fit(dev, ptr(X), N, xld, I0, I1, arr, M, ptr(bufs.ws), bufs.ws_bytes,
-                                         ptr(bufs.table_host), ptr(bufs.table_dev), bufs.table_bytes, stream),
-                  "tr_linear_many_fit")
-            passes += 2 * n
-            if trace is not None:
-                ev[1].record()
-            stops = stop.cpu().numpy()  # the one host sync of the chunk (table_host is free again after it)
-            if trace is not None:
-                trace.append((n, ev[0].elapsed_time(ev[1])))
-        ii += n
-    hist_host = hist.cpu().numpy()
-    for j, mb in enumerate(members):
-        n_run = abs(int(stops[j])) if stops[j] else int(max_iters[j])
-        base = hist_at[j] + len(mb.loss_running)
-        mb.loss_running.extend(hist_host[base:base + n_run].tolist())
-    return [int(s) for s in stops], passes
+
+    def call(ii):
+        check(lib.tr_linear_many_fit(dev, ptr(X), N, xld, I0, I1, arr, M, ptr(bufs.ws), bufs.ws_bytes,
+                                     ptr(bufs.table_host), ptr(bufs.table_dev), bufs.table_bytes, stream),
+              "tr_linear_many_fit")
+
+    # a member's state: its gradient arena (num_params + 2), then m, v and vmax
+    stops, chunks = _run_many_fit(dev, members, rec, ("grad", "exp_avg", "exp_avg_sq", "max_exp_avg_sq"),
+                                  lambda mb: mb.arena.numel() + 2, call, (), sync_every,
+                                  None if trace is None else lambda n, device_ms, _: trace.append((n, device_ms)))
+    return stops, 2 * sum(chunks)
 
 
 SCORE_ROW_BLOCK = _lib.TR_SCORE_ROW_BLOCK  # rows per workgroup of tr_mnl_score_many
@@ -1494,9 +1489,6 @@ def upload_packed(arrays, dtype, dev):
     return out
 
 
-_SCORE_TABLES = {}  # device index -> (pinned host table, device table) of run_score_many
-
-
 def run_score_many(dev, members, want, trace=None):
     """Score many (model, data set) pairs in one call of tr_mnl_score_many.
 
@@ -1517,15 +1509,9 @@ def run_score_many(dev, members, want, trace=None):
     device = f"cuda:{dev}"
     rows = [int(mb.X.shape[0]) for mb in members]
     Cs = [int(mb.n_classes) for mb in members]
+    nbytes = int(lib.tr_score_member_table_bytes(M))
+    table_host, table_dev = table_buffers(dev, nbytes)
     with torch.cuda.device(dev):
-        nbytes = int(lib.tr_score_member_table_bytes(M))
-        # the table's two buffers are kept per device and grown on demand (pinning memory costs more
-        # than a small call); a call ends in a host sync, so the next one finds them free
-        held = _SCORE_TABLES.get(dev)
-        if held is None or held[0].numel() < nbytes:
-            held = _SCORE_TABLES[dev] = (torch.empty(nbytes, dtype=torch.uint8, pin_memory=True),
-                                         torch.empty(nbytes, dtype=torch.uint8, device=device))
-        table_host, table_dev = held
         if want == "predict":
             p_at = np.concatenate([[0], np.cumsum([n * c for n, c in zip(rows, Cs)])])
             n_at = np.concatenate([[0], np.cumsum(rows)])
@@ -1537,8 +1523,7 @@ def run_score_many(dev, members, want, trace=None):
             out = torch.empty(int(c_at[-1]), dtype=torch.uint8, device=device)
             b_at = np.concatenate([[0], np.cumsum([-(-n // SCORE_ROW_BLOCK) for n in rows])])
             parts = torch.empty(2 * int(b_at[-1]), dtype=torch.float64, device=device)
-    arr = (_lib.ScoreMember * M)()
-    rec = np.frombuffer(arr, dtype=np.dtype(_lib.ScoreMember))  # the same memory, column-wise
+    arr, rec = member_records(_lib.ScoreMember, M)
     shapes = np.array([mb.X.shape for mb in members], dtype=np.int64).reshape(M, 3)
     rec["X"] = [mb.X.data_ptr() for mb in members]
     rec["params"] = [mb.arena.data_ptr() + 4 * mb.arena_at for mb in members]

@@ -12,7 +12,7 @@
 #include <cstring>
 
 #include "../../include/tensor_regression_hip.h"
-#include "tr_mnl_resident_table.h"  // AdamScalars, adam_scalars, AdamMemo
+#include "tr_member_table.h"
 
 namespace tr {
 
@@ -136,26 +136,7 @@ inline int check_linear_member(const tr_linear_member& m, bool want_grad, bool w
     return TR_E_ARG;
   }
   if (want_step) {
-    if (m.exp_avg == nullptr || m.exp_avg_sq == nullptr || m.loss_hist == nullptr || m.stop_flag == nullptr) {
-      *why = "NULL buffer";
-      return TR_E_ARG;
-    }
-    if (m.amsgrad && m.max_exp_avg_sq == nullptr) {
-      *why = "amsgrad needs max_exp_avg_sq";
-      return TR_E_ARG;
-    }
-    if (m.n_iters < 0 || m.n_iters > max_iters) {
-      *why = "n_iters outside the call's range";
-      return TR_E_ARG;
-    }
-    if (m.step < 1) {
-      *why = "step must be >= 1";
-      return TR_E_ARG;
-    }
-    if (m.iter < 0 || m.hist_base < 0) {
-      *why = "iter and hist_base must be >= 0";
-      return TR_E_ARG;
-    }
+    if (int rc = check_adam_member(m, max_iters, why)) return rc;
     if (!(m.lr >= 0.0)) {
       *why = "the learning rate must be >= 0";
       return TR_E_ARG;
@@ -201,26 +182,16 @@ inline int build_linear_table(const tr_linear_member* members, int n_members, bo
     t.rank = m.rank;
     t.nonneg[0] = m.nonneg[0] != 0 ? 1 : 0;
     t.nonneg[1] = m.nonneg[1] != 0 ? 1 : 0;
-    t.amsgrad = m.amsgrad ? 1 : 0;
     t.beta = m.softplus_beta;
     t.thr = m.softplus_threshold;
     t.lambda_l2 = m.lambda_l2;
-    t.one_minus_b1 = (float)(1.0 - m.beta1);
-    t.beta2 = (float)m.beta2;
-    t.one_minus_b2 = (float)(1.0 - m.beta2);
-    t.eps = (float)m.eps;
-    t.weight_decay = (float)m.weight_decay;
+    fill_adam_scalars(&t, m.beta1, m.beta2, m.eps, m.weight_decay, m.amsgrad);
     t.n_iters = want_step ? m.n_iters : 0;
     t.hist_base = m.hist_base;
     t.iter0 = m.iter;
     t.patience = m.patience;
     t.tol = m.tol;
-    for (int k = 0; k < t.n_iters; ++k) {
-      const AdamScalars as = memo != nullptr ? memo->at(m.beta1, m.beta2, m.step + k)
-                                             : adam_scalars(m.beta1, m.beta2, m.step + k);
-      t.step_size[k] = (float)(m.lr / as.bc1);
-      t.bc2_sqrt[k] = (float)as.bc2_sqrt;
-    }
+    fill_adam_rows(memo, m.beta1, m.beta2, m.step, t.n_iters, &m.lr, 1, &t.step_size, t.bc2_sqrt);
     if (t.n_iters > 0) ++*n_active;
   }
   return 0;

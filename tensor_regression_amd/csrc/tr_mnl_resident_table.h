@@ -7,13 +7,11 @@
 
 #include <stdint.h>
 
-#include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <tuple>
 
 #include "../../include/tensor_regression_hip.h"
+#include "tr_member_table.h"
 
 namespace tr {
 
@@ -94,33 +92,6 @@ struct ResMember {
   int32_t* stop;
 };
 
-// torch/optim/adam.py (non-capturable): the step's scalars in python-float (double) arithmetic.  The
-// fp32 entry points round each to float; the fp64 one passes them to the fp64 ops unrounded.
-struct AdamScalars {
-  double bc1, bc2_sqrt, one_minus_b1, one_minus_b2;
-};
-inline AdamScalars adam_scalars(double beta1, double beta2, int64_t step) {
-  const double st = (double)step;
-  const double bc2 = 1.0 - std::pow(beta2, st);
-  return {1.0 - std::pow(beta1, st), std::pow(bc2, 0.5), 1.0 - beta1, 1.0 - beta2};
-}
-
-// adam_scalars remembered per (beta1, beta2, step): the members of one table mostly share their betas
-// and all share the step range, so a table costs 2 x 64 pow calls per distinct beta pair, not per member.
-struct AdamMemo {
-  std::map<std::tuple<double, double, int64_t>, AdamScalars> seen;
-  int64_t computed = 0;  // adam_scalars calls made (the stand-alone check counts them)
-  const AdamScalars& at(double beta1, double beta2, int64_t step) {
-    const auto key = std::make_tuple(beta1, beta2, step);
-    auto it = seen.find(key);
-    if (it == seen.end()) {
-      it = seen.emplace(key, adam_scalars(beta1, beta2, step)).first;
-      ++computed;
-    }
-    return it->second;
-  }
-};
-
 // The argument block of n_iters iterations from loop index `iter` (Adam step count `step`, step + 1, ...)
 // on the carve `g`: tr_fit_adam_resident's and every table member's.  `memo` may be NULL.
 inline void fill_res_args(ResArgs* a, const ResGeom& g, const int* nonneg, float sp_beta, float sp_thr,
@@ -133,56 +104,31 @@ inline void fill_res_args(ResArgs* a, const ResGeom& g, const int* nonneg, float
   a->beta = sp_beta;
   a->thr = sp_thr;
   a->lambda_l2 = lambda_l2;
-  a->one_minus_b1 = (float)(1.0 - beta1);
-  a->beta2 = (float)beta2;
-  a->one_minus_b2 = (float)(1.0 - beta2);
-  a->eps = (float)eps;
-  a->weight_decay = (float)weight_decay;
-  a->amsgrad = amsgrad ? 1 : 0;
+  fill_adam_scalars(a, beta1, beta2, eps, weight_decay, amsgrad);
   a->n_iters = n_iters;
   a->hist_base = hist_base;
   a->iter0 = iter;
   a->patience = patience;
   a->tol = tol;
   a->inv_n = (float)(1.0 / (double)g.N);
-  for (int k = 0; k < n_iters; ++k) {  // one row of the table per iteration of the launch
-    const AdamScalars as = memo != nullptr ? memo->at(beta1, beta2, step + k) : adam_scalars(beta1, beta2, step + k);
-    for (int f = 0; f < 3; ++f) a->step_size[f][k] = (float)(lr[f] / as.bc1);
-    a->bc2_sqrt[k] = (float)as.bc2_sqrt;
-  }
+  fill_adam_rows(memo, beta1, beta2, step, n_iters, lr, 3, a->step_size, a->bc2_sqrt);
 }
 
 // The argument checks of one member of tr_fit_adam_resident_many; no device is touched.  Returns 0
 // with the member's carve in *g, or TR_E_ARG / TR_E_UNSUPPORTED with the reason in `why`.
 inline int check_resident_member(const tr_resident_member& m, ResGeom* g, const char** why) {
   *why = "";
-  if (m.X == nullptr || m.target == nullptr || m.params == nullptr || m.weights == nullptr ||
-      m.exp_avg == nullptr || m.exp_avg_sq == nullptr || m.loss_hist == nullptr || m.stop_flag == nullptr) {
+  if (m.X == nullptr || m.target == nullptr || m.params == nullptr || m.weights == nullptr) {
     *why = "NULL buffer";
     return TR_E_ARG;
   }
-  if (m.amsgrad && m.max_exp_avg_sq == nullptr) {
-    *why = "amsgrad needs max_exp_avg_sq";
-    return TR_E_ARG;
-  }
+  if (int rc = check_adam_member(m, RES_MAX_ITERS, why)) return rc;
   if (m.n_rows < 1) {
     *why = "n_rows must be >= 1";
     return TR_E_ARG;
   }
   if (m.x_row_stride < 0) {
     *why = "x_row_stride must be >= 0";
-    return TR_E_ARG;
-  }
-  if (m.n_iters < 0 || m.n_iters > RES_MAX_ITERS) {
-    *why = "n_iters outside [0, 64]";
-    return TR_E_ARG;
-  }
-  if (m.step < 1) {
-    *why = "step must be >= 1";
-    return TR_E_ARG;
-  }
-  if (m.iter < 0 || m.hist_base < 0) {
-    *why = "iter and hist_base must be >= 0";
     return TR_E_ARG;
   }
   for (int f = 0; f < 3; ++f)

@@ -10,7 +10,7 @@ running as gfx950 HIP kernels through the C ABI.
 import numpy as np
 import torch
 
-from . import _engine, _lib
+from . import _engine, _lib, _many
 from ._engine import Plan, as_device_f32, adam_hparams, run_adam_fit
 from .standard_tensor_regression import _plan_for, L2_penalty  # noqa: F401  (L2_penalty re-exported)
 
@@ -666,9 +666,7 @@ def predict_many(models, X=None, Bcp=None, report=None):
     tensor within one CU's LDS; TR_MNL_RESIDENT not 0) is scored in the batch, every other by its own
     `predict`.  report (a dict) receives {'batched': indices, 'alone': indices, 'launches': n}."""
     models = list(models)
-    if report is not None:
-        report.clear()
-        report.update(batched=[], alone=[], launches=0)
+    _many.start_report(report, batched=[], alone=[], launches=0)
     if not models:
         return []
     entries = _score_entries("predict_many", models, X, None, None, Bcp, need_y=False)
@@ -680,9 +678,7 @@ def predict_many(models, X=None, Bcp=None, report=None):
             results[j] = r
     for j in alone:
         results[j] = _alone_predict(entries[j])
-    if report is not None:
-        report.update(batched=batched, alone=alone, launches=1 if batched else 0)
-    return results
+    return _many.finish_many(results, False, report, batched=batched, alone=alone, launches=1 if batched else 0)
 
 
 def score_many(models, X=None, y_true=None, weights=None, report=None):
@@ -696,9 +692,7 @@ def score_many(models, X=None, y_true=None, weights=None, report=None):
     y_true like X (None: each model's own y).  Only the loss sums and the integer counts come back from
     the device, in one packed copy; no probabilities are downloaded."""
     models = list(models)
-    if report is not None:
-        report.clear()
-        report.update(batched=[], alone=[], launches=0)
+    _many.start_report(report, batched=[], alone=[], launches=0)
     if not models:
         return []
     entries = _score_entries("score_many", models, X, y_true, weights, None, need_y=True)
@@ -718,9 +712,7 @@ def score_many(models, X=None, y_true=None, weights=None, report=None):
         for e, (lsum, wsum, counts) in zip(entries, raw):
             results.append({"loss": lsum / wsum, "acc": float(np.trace(counts) / e.N), "counts": counts,
                             "cm": counts / np.sum(counts, axis=0)[None, :]})
-    if report is not None:
-        report.update(batched=batched, alone=alone, launches=1 if batched else 0)
-    return results
+    return _many.finish_many(results, False, report, batched=batched, alone=alone, launches=1 if batched else 0)
 
 
 class _Verbose:

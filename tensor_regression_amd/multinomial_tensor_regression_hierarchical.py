@@ -28,7 +28,7 @@ import types
 import numpy as np
 import torch
 
-from . import _engine
+from . import _engine, _many
 from ._engine import adam_hparams, run_adam_fit_groups
 from . import multinomial_tensor_regression as _mnl
 from .multinomial_tensor_regression import (squeeze_integers, confusion_matrix, idx_to_oneHot,  # noqa: F401
@@ -111,15 +111,7 @@ def _one_schedule(value):
 
 def _per_member(name, value, M):
     """One value for all M models, or a list of M values (ValueError on another length)."""
-    if name == "group_lr":
-        per = isinstance(value, list) and not _one_schedule(value)
-    else:
-        per = isinstance(value, (list, tuple))
-    if not per:
-        return [value] * M
-    if len(value) != M:
-        raise ValueError(f"{name}: a list must hold one value per model ({M}), got {len(value)}")
-    return list(value)
+    return _many.per_member(name, value, M, _one_schedule if name == "group_lr" else None)
 
 
 def fit_Adam_many(models, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, verbose=False, Adam_kwargs=None,
@@ -140,20 +132,11 @@ def fit_Adam_many(models, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, 
     verbose=2 (a line per iteration) is not offered: it would force one launch per iteration."""
     models = list(models)
     M = len(models)
-    if verbose == 2:
-        raise NotImplementedError("fit_Adam_many: verbose=2 prints every iteration, which forces one launch per "
-                                  "iteration per model; call fit_Adam on each model instead")
+    _many.check_models(models, CP_logistic_regression, verbose, ", which forces one launch per iteration per model")
     given = dict(lambda_L2=lambda_L2, max_iter=max_iter, tol=tol, patience=patience, Adam_kwargs=Adam_kwargs,
                  group_lr=group_lr)
     args = {k: _per_member(k, v, M) for k, v in given.items()}
-    if len({id(m) for m in models}) != M:
-        raise ValueError("fit_Adam_many: the same model object appears twice")
-    for m in models:
-        if not isinstance(m, CP_logistic_regression):
-            raise TypeError(f"fit_Adam_many takes this module's CP_logistic_regression objects, got {type(m).__name__}")
-    if report is not None:
-        report.clear()
-        report.update(batched=[], alone=[], launches=0)
+    _many.start_report(report, batched=[], alone=[], launches=0)
     if M == 0:
         return []
     # every member's own argument errors, in fit_Adam's order, before anything is launched
@@ -179,10 +162,9 @@ def fit_Adam_many(models, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, 
         inside = (on and len(m.Bcp) == N_GROUPS and getattr(m.X, "ndim", 0) == 3 and int(m.X.shape[0]) <= _engine.resident_max_rows(
             m.Bcp[0].shape[0], m.Bcp[1].shape[0], m.Bcp[2].shape[0], m.Bcp[0].shape[1]))
         (batched if inside else alone).append(j)
-    results = [False] * M
-    launches = 0
+    results, launches = [False] * M, 0
     if batched:
-        members, srcs, offsets, total = [], [], [], 0
+        members, params = [], []
         for j in batched:
             m = models[j]
             _, Xd, yd = m._device_data()
@@ -198,34 +180,22 @@ def fit_Adam_many(models, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, 
                 breaks=sorted({s for starts, _ in schedules[j] for s in starts[1:]}), max_iter=args["max_iter"][j],
                 tol=args["tol"][j], patience=args["patience"][j], loss_running=m.loss_running,
                 w=m.weights.to(f"cuda:{dev}", torch.float32).contiguous())
-            for f, A in enumerate(m.Bcp):
-                A = torch.as_tensor(A)
+            factors = [torch.as_tensor(A) for A in m.Bcp]
+            for f, A in enumerate(factors):
                 if tuple(A.shape) != (dims[f], R):
                     raise ValueError(f"factor {f} has shape {tuple(A.shape)}, expected {(dims[f], R)}")
-                srcs.append(A.detach().reshape(-1))
-                offsets.append(total)
-                total += dims[f] * R
             members.append(mb)
-        # every member's factors in ONE arena (one launch to pack, one to write back), a slice each
-        arena = _engine._pack_arena(srcs, total, torch.float32, f"cuda:{dev}")
-        bounds = offsets + [total]
-        for k, mb in enumerate(members):
-            mb.arena = arena[bounds[3 * k]:bounds[3 * k + 3]]
+            params.append(factors)
+        arena, offsets, slices = _many.pack_members(params, f"cuda:{dev}")
+        for mb, own in zip(members, slices):
+            mb.arena = own
         stops, launches = _engine.run_resident_many(dev, members)
-        _engine._unpack_arena(arena, offsets, [A for j in batched for A in models[j].Bcp])
+        _many.unpack_members(arena, offsets, [models[j].Bcp for j in batched])
         for j, s in zip(batched, stops):
             results[j] = s > 0
     for j in alone:  # outside the envelope (or the route switched off): the model's own fit, one after another
-        results[j] = models[j].fit_Adam(lambda_L2=args["lambda_L2"][j], max_iter=args["max_iter"][j],
-                                        tol=args["tol"][j], patience=args["patience"][j], verbose=False,
-                                        Adam_kwargs=args["Adam_kwargs"][j], group_lr=args["group_lr"][j])
-    if (verbose is True) or (verbose >= 1):
-        for j, conv in enumerate(results):
-            print(f"model {j}: " + ('Convergence reached' if conv else
-                                    'Reached maximum number of iterations without convergence'))
-    if report is not None:
-        report.update(batched=batched, alone=alone, launches=launches)
-    return results
+        results[j] = models[j].fit_Adam(verbose=False, **{k: v[j] for k, v in args.items()})
+    return _many.finish_many(results, verbose, report, batched=batched, alone=alone, launches=launches)
 
 
 class CP_logistic_regression(_mnl.CP_logistic_regression):

@@ -20,7 +20,7 @@ import types
 import numpy as np
 import torch
 
-from . import _engine, _lib
+from . import _engine, _lib, _many
 from ._engine import Plan, as_device_f32, adam_hparams, run_adam_fit
 
 __all__ = ["make_BcpInit", "non_neg_fn", "lin_model", "stepwise_model", "L2_penalty",
@@ -401,13 +401,7 @@ class CP_linear_regression():
 LINEAR_MANY_MIN_BATCH = 4
 
 
-def _per_member(name, value, M):
-    """One value for all M models, or a list of M values (ValueError on another length)."""
-    if not isinstance(value, (list, tuple)):
-        return [value] * M
-    if len(value) != M:
-        raise ValueError(f"{name}: a list must hold one value per model ({M}), got {len(value)}")
-    return list(value)
+_per_member = _many.per_member
 
 
 def _targets(y, M):
@@ -445,24 +439,15 @@ def fit_Adam_many(models, X, y, lambda_L2=0.01, max_iter=1000, tol=1e-5, patienc
     from .util import HostStream
     models = list(models)
     M = len(models)
-    if verbose == 2:
-        raise NotImplementedError("fit_Adam_many: verbose=2 prints every iteration of every model; call fit_Adam "
-                                  "on each model instead")
+    _many.check_models(models, CP_linear_regression, verbose, " of every model")
     given = dict(lambda_L2=lambda_L2, max_iter=max_iter, tol=tol, patience=patience, Adam_kwargs=Adam_kwargs)
     args = {k: _per_member(k, v, M) for k, v in given.items()}
     ys, shared_y = _targets(y, M)
-    if len({id(m) for m in models}) != M:
-        raise ValueError("fit_Adam_many: the same model object appears twice")
-    for m in models:
-        if not isinstance(m, CP_linear_regression):
-            raise TypeError(f"fit_Adam_many takes this module's CP_linear_regression objects, got {type(m).__name__}")
     if min_batch is None:
         min_batch = LINEAR_MANY_MIN_BATCH
     if int(min_batch) < 1:
         raise ValueError(f"min_batch must be >= 1, got {min_batch}")
-    if report is not None:
-        report.clear()
-        report.update(batched=[], alone=[], groups=0, x_passes=0)
+    _many.start_report(report, batched=[], alone=[], groups=0, x_passes=0)
     if M == 0:
         return []
     hps = [adam_hparams(ak) for ak in args["Adam_kwargs"]]  # TypeError on None, as fit_Adam
@@ -496,9 +481,7 @@ def fit_Adam_many(models, X, y, lambda_L2=0.01, max_iter=1000, tol=1e-5, patienc
     groups = [g for g in groups if len(g) >= int(min_batch)]
     batched = [j for g in groups for j in g]
     alone = [j for j in range(M) if j not in set(batched)]
-    results = [False] * M
-    passes = 0
-    y_dev = {}
+    results, passes, y_dev = [False] * M, 0, {}
 
     def target(j):  # a shared y is uploaded once
         key = 0 if shared_y else j
@@ -507,21 +490,16 @@ def fit_Adam_many(models, X, y, lambda_L2=0.01, max_iter=1000, tol=1e-5, patienc
         return y_dev[key]
 
     for g in groups:
-        members, srcs, offsets, total = [], [], [], 0
+        members, params = [], []
         for j in g:
             m = models[j]
             R = int(m.Bcp[0].shape[1])
             nn, beta, thr = _engine.nonlin_key(m.non_negative, m.softplus_kwargs, 2)
-            for f, A in enumerate(m.Bcp):
-                A = torch.as_tensor(A)
+            factors = [torch.as_tensor(A) for A in m.Bcp]
+            for f, A in enumerate(factors):
                 if tuple(A.shape) != ((I0, I1)[f], R):
                     raise ValueError(f"model {j}: factor {f} has shape {tuple(A.shape)}, expected {((I0, I1)[f], R)}")
-                srcs.append(A.detach().reshape(-1))
-                offsets.append(total)
-                total += A.numel()
-            srcs.append(torch.as_tensor(m.bias).detach().reshape(-1)[:1])
-            offsets.append(total)
-            total += 1
+            params.append(factors + [torch.as_tensor(m.bias).detach().reshape(-1)[:1]])
             w = torch.as_tensor(m.weights).to(f"cuda:{dev}", torch.float32).contiguous()
             if w.numel() != R:
                 raise ValueError(f"model {j}: weights holds {w.numel()} values, the rank is {R}")
@@ -529,24 +507,15 @@ def fit_Adam_many(models, X, y, lambda_L2=0.01, max_iter=1000, tol=1e-5, patienc
                 y=target(j), w=w, rank=R, nonneg=nn, beta=beta, thr=thr, lambda_L2=args["lambda_L2"][j], hp=hps[j],
                 max_iter=args["max_iter"][j], tol=args["tol"][j], patience=args["patience"][j],
                 loss_running=m.loss_running))
-        # every member's parameters in ONE arena (one launch to pack, one to write back), a slice each
-        arena = _engine._pack_arena(srcs, total, torch.float32, f"cuda:{dev}")
-        bounds = offsets + [total]
-        for k, mb in enumerate(members):
-            mb.arena = arena[bounds[3 * k]:bounds[3 * k + 3]]
+        arena, offsets, slices = _many.pack_members(params, f"cuda:{dev}")
+        for mb, own in zip(members, slices):
+            mb.arena = own
         stops, n_pass = _engine.run_linear_many(dev, X, members)
         passes += n_pass
-        _engine._unpack_arena(arena, offsets, [t for j in g for t in (*models[j].Bcp, models[j].bias)])
+        _many.unpack_members(arena, offsets, [(*models[j].Bcp, models[j].bias) for j in g])
         for j, s in zip(g, stops):
             results[j] = s > 0
     for j in alone:  # outside the envelope, a small group or the route switched off: the model's own fit
-        results[j] = models[j].fit_Adam(X, ys[j], lambda_L2=args["lambda_L2"][j], max_iter=args["max_iter"][j],
-                                        tol=args["tol"][j], patience=args["patience"][j], verbose=False,
-                                        Adam_kwargs=args["Adam_kwargs"][j])
-    if (verbose is True) or (verbose >= 1):
-        for j, conv in enumerate(results):
-            print(f"model {j}: " + ('Convergence reached' if conv else
-                                    'Reached maximum number of iterations without convergence'))
-    if report is not None:
-        report.update(batched=batched, alone=alone, groups=len(groups), x_passes=passes)
-    return results
+        results[j] = models[j].fit_Adam(X, ys[j], verbose=False, **{k: v[j] for k, v in args.items()})
+    return _many.finish_many(results, verbose, report, batched=batched, alone=alone, groups=len(groups),
+                             x_passes=passes)

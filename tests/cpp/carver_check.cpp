@@ -7,18 +7,10 @@
 #include <cstdlib>
 #include <vector>
 
+#include "check.h"
 #include "tr_workspace.h"
 
 namespace {
-
-int g_failed = 0;
-#define CHECK(cond)                                                          \
-  do {                                                                       \
-    if (!(cond)) {                                                           \
-      std::fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #cond); \
-      ++g_failed;                                                            \
-    }                                                                        \
-  } while (0)
 
 size_t al(size_t b) { return (b + 255) / 256 * 256; }
 

@@ -9,18 +9,10 @@
 #include <cstring>
 #include <vector>
 
+#include "adam_rows_check.h"  // with check.h
 #include "tr_linear_many.h"
 
 namespace {
-
-int g_failed = 0;
-#define CHECK(cond)                                                          \
-  do {                                                                       \
-    if (!(cond)) {                                                           \
-      std::fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #cond); \
-      ++g_failed;                                                            \
-    }                                                                        \
-  } while (0)
 
 // never dereferenced by the host code: distinct non-NULL addresses inside static blocks
 float g_f[16];
@@ -107,6 +99,7 @@ void check_geom(int64_t N, int64_t I0, int64_t I1) {
 
 int main() {
   using namespace tr;
+  check_adam_rows();
   // the envelope's edges
   CHECK(linear_many_envelope(8, 12, 0, 32) && !linear_many_envelope(8, 12, 0, 33) && !linear_many_envelope(8, 12, 0, 0));
   CHECK(!linear_many_envelope(3, 3, 0, 2) && linear_many_envelope(3, 4, 0, 2));        // P % 4

@@ -9,18 +9,10 @@
 #include <cstring>
 #include <vector>
 
+#include "adam_rows_check.h"  // with check.h
 #include "tr_mnl_resident_table.h"
 
 namespace {
-
-int g_failed = 0;
-#define CHECK(cond)                                                          \
-  do {                                                                       \
-    if (!(cond)) {                                                           \
-      std::fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #cond); \
-      ++g_failed;                                                            \
-    }                                                                        \
-  } while (0)
 
 struct Shape {
   int64_t N, I0, I1;
@@ -120,6 +112,7 @@ void check_carve(const tr::ResGeom& g) {
 
 int main() {
   using namespace tr;
+  check_adam_rows();
   const int64_t nmax = max_rows(8, 12, 4, 6);
   CHECK(nmax >= 227 && nmax < 65536);
   const std::vector<Shape> shapes = {{1, 2, 3, 2, 1},   {5, 3, 4, 3, 2},   {37, 2, 5, 2, 3}, {40, 8, 12, 4, 6},

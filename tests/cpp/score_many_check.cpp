@@ -10,19 +10,11 @@
 #include <cstring>
 #include <vector>
 
+#include "adam_rows_check.h"  // with check.h
 #include "tr_mnl_resident_table.h"
 #include "tr_mnl_score_table.h"
 
 namespace {
-
-int g_failed = 0;
-#define CHECK(cond)                                                          \
-  do {                                                                       \
-    if (!(cond)) {                                                           \
-      std::fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #cond); \
-      ++g_failed;                                                            \
-    }                                                                        \
-  } while (0)
 
 struct Shape {
   int64_t N, I0, I1;
@@ -131,6 +123,7 @@ int build(const std::vector<tr_score_member>& ms, tr::ScoreMember* table, int64_
 
 int main() {
   using namespace tr;
+  check_adam_rows();  // (this route writes no Adam rows; the resident header it includes for the envelope does)
   CHECK(SCORE_ROWS == TR_SCORE_ROW_BLOCK && SCORE_ROWS % (SCORE_T / 64) == 0);
 
   // ---- the envelope: a superset of the resident fit's, at every rank and class count ----
