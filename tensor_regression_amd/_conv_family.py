@@ -2,8 +2,9 @@
 convolutional_ and convolutional_fourier_tensor_regression): the helper functions all of them use,
 the plan cache, and two base classes.
 
-  ConvModelBase     constructor body, plan / input plumbing, the LBFGS loop, the Adam tail, predict
-                    and the post-hoc methods every model has.
+  ConvModelBase     constructor body, plan / input plumbing, both fits (their loop, printer and end
+                    are _fit's, shared with the other modules), predict and the post-hoc methods
+                    every model has.
   SmoothConvModel   what the phase and Fourier models add to it alike: the smoothness arguments of
                     both fits, `self.optimizer`, `y_spectrum`, get_params / set_params / detach_Bcp.
 
@@ -15,10 +16,9 @@ set in the public module of the model it belongs to.
 import numpy as np
 import torch
 
-from . import _engine
+from . import _engine, _fit
 from ._engine import adam_hparams, as_device_f32, run_adam_fit
 
-_DEFAULT_SOFTPLUS = {'beta': 50, 'threshold': 1}
 _OWN = object()  # _plan_for: the model's own softplus_kwargs
 
 
@@ -49,7 +49,7 @@ def non_neg_fn(B_cp, non_negative, softplus_kwargs=None):
     """Yield softplus(A_k) for flagged factors, A_k otherwise (…py:67-93; None = beta 50 / threshold 1
     here, where the reference would fail on `**None`)."""
     if softplus_kwargs is None:
-        softplus_kwargs = _DEFAULT_SOFTPLUS
+        softplus_kwargs = _fit.DEFAULT_SOFTPLUS
     for A, nn in zip(B_cp, non_negative):
         yield torch.nn.functional.softplus(A, **softplus_kwargs) if nn else A
 
@@ -108,22 +108,6 @@ def _cached_plan(plan_cls, shape, rows, non_negative, softplus_kwargs, dev):
     return p
 
 
-class _VerbosePrinter:
-    """The per-iteration verbose print of fit_Adam, from the kernel's y_hat."""
-
-    def __init__(self, plan, X, target, y, norm, line):
-        self.plan, self.X, self.t, self.norm, self.line = plan, X, target, norm, line
-        self.var_y = torch.var(y).item()
-        self.grad = torch.zeros(plan.num_grads, dtype=torch.float32, device=X.device)
-        self.yhat = torch.empty_like(target)
-
-    def before_step(self, arena):
-        self.plan.loss_grad(self.X, self.t, None, self.norm, arena, None, self.grad, yhat=self.yhat)
-
-    def after_step(self, ii, loss):
-        print(self.line(ii, loss, torch.var(self.yhat).item() / self.var_y))
-
-
 ####################################
 ########## Base classes ############
 ####################################
@@ -154,20 +138,14 @@ class ConvModelBase:
                                       device=device)
         else:
             self.weights = torch.tensor(weights, dtype=self.dtype, requires_grad=False, device=device)
-        self.softplus_kwargs = dict(_DEFAULT_SOFTPLUS) if softplus_kwargs is None else softplus_kwargs
+        self.softplus_kwargs = _fit.softplus_or_default(softplus_kwargs)
         self.rank_normal = rank_normal
         self.temporal_window = temporal_window
         self.idx_conv = self.get_idxConv(X_shape[0]).to(device)
         self.rank_spectral = rank_spectral
         self.rank = rank_normal + rank_spectral
         self.device = device
-        n_flags = len(X_shape) + len(y_shape[1:])
-        if non_negative is True:
-            self.non_negative = [True] * n_flags
-        elif non_negative is False:
-            self.non_negative = [False] * n_flags
-        else:
-            self.non_negative = non_negative
+        self.non_negative = _fit.non_negative_flags(non_negative, len(X_shape) + len(y_shape[1:]))
         self.bias = torch.zeros(y_shape[1:], dtype=self.dtype, requires_grad=True, device=device)
         self.y_shape = y_shape
         B_dims = list(X_shape[1:]) + list(y_shape[1:])
@@ -238,13 +216,8 @@ class ConvModelBase:
         target = y[W // 2: y.shape[0] - W // 2]  # y[idx_conv]: a contiguous block of rows
         return X, y, target, dev
 
-    def _set_grads(self, plan, gtot):
-        o = plan.offsets
-        for f, A in enumerate(list(self.Bcp_n) + list(self.Bcp_w)):
-            A.grad = gtot[o[f]:o[f + 1]].to(A.device).clone().view(A.shape)
-        self.bias.grad = gtot[o[4]:].to(self.bias.device).clone().view(self.bias.shape)
-
     def _parameters(self):
+        """The torch leaves in arena order, the bias last."""
         return list(self.Bcp_n) + list(self.Bcp_w) + [self.bias]
 
     # ---- fitting -----------------------------------------------------------------------------
@@ -254,56 +227,35 @@ class ConvModelBase:
         pass with self.softplus_kwargs; logs the total loss.  `penalties`: _set_penalties' arguments
         after (plan, target), for the models that have it."""
         self._check_offered(X, verbose)
-        if LBFGS_kwargs is None:
-            raise TypeError("torch.optim.lbfgs.LBFGS() argument after ** must be a mapping, not NoneType")
+        _fit.require_lbfgs_kwargs(LBFGS_kwargs)
         lam = self._lambda_fit(lambda_L2)
         X, y, target, dev = self._inputs(X, y)
         plan = self._plan_for(X, dev)
         if penalties is not None:
             self._set_penalties(plan, target, *penalties)
-        optimizer = torch.optim.LBFGS(self._parameters(), **LBFGS_kwargs)
-        if self._keeps_optimizer:
-            self.optimizer = optimizer
-        opts = dict(dtype=torch.float32, device=f"cuda:{dev}")
-        grad = torch.zeros(plan.num_grads, **opts)
-        gtot = torch.zeros(plan.num_params, **opts)
-        loss_out = torch.zeros(1, **opts)
+        grad, gtot, loss_out = _fit.lbfgs_buffers(plan, dev)
         yhat = torch.empty_like(target)
         norm = float(target.numel())
         chatty = verbose in self._verbose_levels
         var_y = torch.var(y).item() if chatty else None
+        params = self._parameters()
 
-        def total_loss(with_grads):
+        def total_loss(with_grads=True):
             arena = plan.pack(self.Bcp_w, self.Bcp_n, self.bias)
             plan.loss_grad(X, target, None, norm, arena, None, grad, yhat=yhat)
             plan.finalize_grad(arena, grad, lam, gtot, loss_out)
             if with_grads:
-                self._set_grads(plan, gtot)
+                _fit.set_factor_grads(plan, gtot, params[:-1], self.bias)
             return loss_out[0].clone()
 
-        def closure():
-            optimizer.zero_grad()
-            return total_loss(True)
+        def log_loss(ii):
+            loss = total_loss(False).item()
+            return loss, (self._verbose_line(ii, loss, torch.var(yhat).item() / var_y) if chatty else None)
 
-        convergence_reached = False
-        for ii in range(max_iter):
-            if ii % running_loss_logging_interval == 0:
-                self.loss_running.append(total_loss(False).item())
-                if chatty:
-                    print(self._verbose_line(ii, self.loss_running[-1], torch.var(yhat).item() / var_y))
-            if len(self.loss_running) > patience:
-                if np.sum(np.abs(np.diff(self.loss_running[-patience + 1:]))) < tol:
-                    convergence_reached = True
-                    break
-            elif np.isnan(self.loss_running[-1]):
-                convergence_reached = False
-                print('Loss is NaN. Stopping.')
-                break
-            optimizer.step(closure)
-        if (verbose is True) or (verbose >= 1):
-            print('Convergence reached' if convergence_reached else
-                  'Reached maximum number of iterations without convergence')
-        return convergence_reached
+        keep = (lambda optimizer: setattr(self, "optimizer", optimizer)) if self._keeps_optimizer else None
+        return _fit.lbfgs_fit(params, LBFGS_kwargs, total_loss, log_loss, stop="length", max_iter=max_iter, tol=tol,
+                              patience=patience, running_loss_logging_interval=running_loss_logging_interval,
+                              verbose=verbose, loss_running=self.loss_running, on_optimizer=keep)
 
     def _fit_adam(self, X, y, lambda_L2, max_iter, tol, patience, verbose, Adam_kwargs, process_group,
                   penalties=None):
@@ -319,17 +271,12 @@ class ConvModelBase:
             self.optimizer = torch.optim.Adam(self._parameters(), **Adam_kwargs)
         norm = float(target.numel())
         arena = plan.pack(self.Bcp_w, self.Bcp_n, self.bias)
-        vcb = _VerbosePrinter(plan, X, target, y, norm, self._verbose_line) \
+        vcb = _fit.VerbosePrinter(self._verbose_line, y, _fit.yhat_from_loss_grad(plan, X, target, norm, None)) \
             if verbose in self._verbose_levels else None
         convergence_reached, _ = run_adam_fit(plan, X, target, None, norm, arena, None, lam, max_iter, tol, patience,
                                               hp, self.loss_running, verbose_cb=vcb)
         plan.unpack_into(arena, self.Bcp_w, self.Bcp_n, self.bias)
-        if plan.last_stop < 0:
-            print('Loss is NaN. Stopping.')
-        if (verbose is True) or (verbose >= 1):
-            print('Convergence reached' if convergence_reached else
-                  'Reached maximum number of iterations without convergence')
-        return convergence_reached
+        return _fit.finish_fit(convergence_reached, verbose, nan_stopped=plan.last_stop < 0)
 
     ####################################
     ############ POST-HOC ##############
@@ -365,12 +312,7 @@ class ConvModelBase:
         print('loss_running:', self.loss_running)
 
     def plot_outputs(self):
-        import matplotlib.pyplot as plt
-        plt.figure()
-        plt.plot(self.loss_running)
-        plt.xlabel('logged iteration')
-        plt.ylabel('loss')
-        plt.title('loss')
+        plt = _fit.plot_loss(self.loss_running)
         Bcp_n_final, Bcp_w_final = self.return_Bcp_final()
         fig, axs = plt.subplots(len(Bcp_n_final) + len(Bcp_w_final))
         for ii, val in enumerate(Bcp_n_final + Bcp_w_final):

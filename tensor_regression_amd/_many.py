@@ -6,7 +6,7 @@ import itertools
 
 import torch
 
-from . import _engine
+from . import _engine, _fit
 
 
 def per_member(name, value, M, one_value=None):
@@ -64,8 +64,7 @@ def finish_many(results, verbose, report, **report_fields):
     convergence_reached), `report` updated with the call's fields; returns `results`."""
     if (verbose is True) or (verbose >= 1):
         for j, conv in enumerate(results):
-            print(f"model {j}: " + ('Convergence reached' if conv else
-                                    'Reached maximum number of iterations without convergence'))
+            print(f"model {j}: " + _fit.convergence_line(conv))
     if report is not None:
         report.update(report_fields)
     return results

@@ -10,7 +10,7 @@ running as gfx950 HIP kernels through the C ABI.
 import numpy as np
 import torch
 
-from . import _engine, _lib, _many
+from . import _engine, _fit, _lib, _many
 from ._engine import Plan, as_device_f32, adam_hparams, run_adam_fit
 from .standard_tensor_regression import _plan_for, L2_penalty  # noqa: F401  (L2_penalty re-exported)
 
@@ -89,30 +89,25 @@ def model(X, Bcp, weights, non_negative, softplus_kwargs=None):
 ####################################
 
 class CP_logistic_regression():
+    _takes_host_stream = True  # (the hierarchical module's constructor does not)
+
     def __init__(self, X, y, rank=5, non_negative=False, weights=None, Bcp_init=None, Bcp_init_scale=1,
                  device='cpu', softplus_kwargs=None):
         """(multinomial_tensor_regression.py:212-286; same arguments and attributes).  X may also
         be a util.HostStream (host-resident X streamed through HBM every iteration; fit_Adam and
         predict only)."""
         from .util import HostStream
-        self.X = X if isinstance(X, HostStream) else torch.as_tensor(X, dtype=torch.float32).to(device)
+        self.X = X if self._takes_host_stream and isinstance(X, HostStream) else \
+            torch.as_tensor(X, dtype=torch.float32).to(device)
         self.y = torch.as_tensor(y, dtype=torch.long).to(device)
         if weights is None:
             self.weights = torch.ones((rank), device=device)
         else:
             self.weights = torch.tensor(weights)
-        if softplus_kwargs is None:
-            self.softplus_kwargs = {'beta': 50, 'threshold': 1}
-        else:
-            self.softplus_kwargs = softplus_kwargs
+        self.softplus_kwargs = _fit.softplus_or_default(softplus_kwargs)
         self.rank = rank
         self.device = device
-        if non_negative is True:
-            self.non_negative = [True] * (self.X.ndim)
-        elif non_negative is False:
-            self.non_negative = [False] * (self.X.ndim)
-        else:
-            self.non_negative = non_negative
+        self.non_negative = _fit.non_negative_flags(non_negative, self.X.ndim)
         self.n_classes = len(torch.unique(self.y))
         B_dims = np.concatenate((np.array(self.X.shape[1:]), [self.n_classes]))
         # a class factor drawn here from the LOCAL labels may be widened to the global class set
@@ -240,46 +235,30 @@ class CP_logistic_regression():
     def fit(self, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, weights=None, verbose=False,
             running_loss_logging_interval=10, LBFGS_kwargs=None):
         """LBFGS fit (multinomial_tensor_regression.py:291-387); closures evaluated on gfx950."""
-        if LBFGS_kwargs is None:
-            raise TypeError("torch.optim.lbfgs.LBFGS() argument after ** must be a mapping, not NoneType")
+        _fit.require_lbfgs_kwargs(LBFGS_kwargs)
         dev, Xd, yd = self._device_data()
         if not isinstance(Xd, torch.Tensor):
             raise NotImplementedError("the LBFGS fit needs X resident on the device (use fit_Adam for a HostStream)")
         plan = self._get_plan(Xd, Xd.shape[0])
         cw, W = self._class_weights(weights, dev, yd)
-        optimizer = torch.optim.LBFGS(self.Bcp, **LBFGS_kwargs)
         w = self.weights.to(f"cuda:{dev}", torch.float32).contiguous()
-        opts = dict(dtype=torch.float32, device=f"cuda:{dev}")
-        grad = torch.zeros(plan.num_grads, **opts)
-        gtot = torch.zeros(plan.num_params, **opts)
-        loss_out = torch.zeros(1, **opts)
+        grad, gtot, loss_out = _fit.lbfgs_buffers(plan, dev)
 
-        def closure():
-            optimizer.zero_grad()
+        def closure_loss():
             arena = plan.pack(self.Bcp)
             plan.loss_grad(Xd, yd, cw, W, arena, w, grad)
             plan.finalize_grad(arena, grad, lambda_L2, gtot, loss_out)
-            for A, g in zip(self.Bcp, plan.factor_views(gtot)):
-                A.grad = g.to(A.device).clone()
+            _fit.set_factor_grads(plan, gtot, self.Bcp)
             return loss_out[0].clone()
 
-        convergence_reached = False
-        for ii in range(max_iter):
-            if ii % running_loss_logging_interval == 0:
-                arena = plan.pack(self.Bcp)
-                plan.loss_grad(Xd, yd, cw, W, arena, w, grad)  # data loss only (reference :372)
-                self.loss_running.append(float(grad[plan.num_params].item()))
-                if verbose == 2:
-                    print(f'Iteration: {ii}, Loss: {self.loss_running[-1]}')
-            if ii > patience:
-                if np.sum(np.abs(np.diff(self.loss_running[ii - patience:]))) < tol:
-                    convergence_reached = True
-                    break
-            optimizer.step(closure)
-        if (verbose is True) or (verbose >= 1):
-            print('Convergence reached' if convergence_reached else
-                  'Reached maximum number of iterations without convergence')
-        return convergence_reached
+        def log_loss(ii):
+            plan.loss_grad(Xd, yd, cw, W, plan.pack(self.Bcp), w, grad)  # data loss only (reference :372)
+            loss = float(grad[plan.num_params].item())
+            return loss, (_fit.line_plain(ii, loss) if verbose == 2 else None)
+
+        return _fit.lbfgs_fit(self.Bcp, LBFGS_kwargs, closure_loss, log_loss, stop="index", max_iter=max_iter,
+                              tol=tol, patience=patience, running_loss_logging_interval=running_loss_logging_interval,
+                              verbose=verbose, loss_running=self.loss_running)
 
     def fit_Adam(self, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, weights=None, verbose=False,
                  Adam_kwargs=None, process_group=None):
@@ -294,25 +273,19 @@ class CP_logistic_regression():
             plan = self._get_plan(Xd, Xd.shape[0])
             cw, W = self._class_weights(weights, dev, yd)
             return dev, Xd, yd, plan, cw, W
-        if process_group is None:
-            dev, Xd, yd, plan, cw, W = prepare()
-        else:
+        if process_group is not None:
             # collectives first, then the rank-local checks with a collective verdict: a failure on
             # one rank raises on every rank instead of leaving the others in a later all-reduce
             self._sync_class_set(process_group)
-            (dev, Xd, yd, plan, cw, _), W = _engine.fit_start(process_group, prepare, lambda o: o[5],
-                                                              lambda o: o[3].num_params)
+        (dev, Xd, yd, plan, cw, _), W = _fit.start_adam(process_group, prepare, lambda o: o[5], lambda o: o[3])
         arena = plan.pack(self.Bcp)
         w = self.weights.to(f"cuda:{dev}", torch.float32).contiguous()
-        vcb = _Verbose() if verbose == 2 else None
+        vcb = _fit.VerbosePrinter(_fit.line_plain) if verbose == 2 else None
         convergence_reached, _ = run_adam_fit(plan, Xd, yd, cw, W, arena, w, lambda_L2, max_iter, tol, patience,
                                               hp, self.loss_running, verbose_cb=vcb, process_group=process_group,
                                               arena_checked=True)
         plan.unpack_into(arena, self.Bcp)
-        if (verbose is True) or (verbose >= 1):
-            print('Convergence reached' if convergence_reached else
-                  'Reached maximum number of iterations without convergence')
-        return convergence_reached
+        return _fit.finish_fit(convergence_reached, verbose)
 
     def predict(self, X=None, y_true=None, Bcp=None, device=None):
         """(probabilities, argmax) as numpy (multinomial…py:474-545); the 'logit' the reference
@@ -327,18 +300,7 @@ class CP_logistic_regression():
             logit = torch.cat([model(Xc, Bd, self.weights, self.non_negative, softplus_kwargs=self.softplus_kwargs)
                                for _, _, Xc in X.chunks()]).detach().cpu().numpy()
             return logit, np.argmax(logit, axis=1)
-        if isinstance(X, torch.Tensor) is False:
-            X = torch.tensor(X, dtype=torch.float32, requires_grad=False).to(device)
-        elif X.device != torch.device(device):
-            X = X.to(device)
-        if Bcp is None:
-            Bcp = self.Bcp
-        elif isinstance(Bcp[0], torch.Tensor) is False:
-            for ii in range(len(Bcp)):
-                Bcp[ii] = torch.tensor(Bcp[ii], dtype=torch.float32, requires_grad=False).to(device)
-        elif Bcp[0].device != torch.device(device):
-            for ii in range(len(Bcp)):
-                Bcp[ii] = Bcp[ii].to(device)
+        X, Bcp = _fit.coerce_predict_inputs(X, Bcp, self.Bcp, device)
         dev = _engine.compute_device(X, device)
         Xd = _engine.as_device_rows(X, dev)
         logit = model(Xd, [torch.as_tensor(A).to(f"cuda:{dev}") for A in Bcp], self.weights, self.non_negative,
@@ -407,12 +369,7 @@ class CP_logistic_regression():
         print('loss_running:', self.loss_running)
 
     def plot_outputs(self):
-        import matplotlib.pyplot as plt
-        plt.figure()
-        plt.plot(self.loss_running)
-        plt.xlabel('logged iteration')
-        plt.ylabel('loss')
-        plt.title('loss')
+        plt = _fit.plot_loss(self.loss_running)
         logit, pred = self.predict()
         fig, axs = plt.subplots(2)
         axs[0].imshow(idx_to_oneHot(pred, self.n_classes), aspect='auto', interpolation='none')
@@ -713,13 +670,3 @@ def score_many(models, X=None, y_true=None, weights=None, report=None):
             results.append({"loss": lsum / wsum, "acc": float(np.trace(counts) / e.N), "counts": counts,
                             "cm": counts / np.sum(counts, axis=0)[None, :]})
     return _many.finish_many(results, False, report, batched=batched, alone=alone, launches=1 if batched else 0)
-
-
-class _Verbose:
-    """verbose==2 print of the multinomial fit_Adam (multinomial…py:460-461)."""
-
-    def before_step(self, arena):
-        pass
-
-    def after_step(self, ii, loss):
-        print(f'Iteration: {ii}, Loss: {loss}')

@@ -28,11 +28,11 @@ import types
 import numpy as np
 import torch
 
-from . import _engine, _many
+from . import _engine, _fit, _many
 from ._engine import adam_hparams, run_adam_fit_groups
 from . import multinomial_tensor_regression as _mnl
 from .multinomial_tensor_regression import (squeeze_integers, confusion_matrix, idx_to_oneHot,  # noqa: F401
-                                            make_BcpInit, non_neg_fn, model, L2_penalty, _Verbose,
+                                            make_BcpInit, non_neg_fn, model, L2_penalty,
                                             predict_many, score_many)
 
 __all__ = ["squeeze_integers", "confusion_matrix", "idx_to_oneHot", "make_BcpInit", "non_neg_fn", "model",
@@ -199,36 +199,14 @@ def fit_Adam_many(models, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, 
 
 
 class CP_logistic_regression(_mnl.CP_logistic_regression):
+    _takes_host_stream = False
+
     def __init__(self, X, y, rank=5, non_negative=False, weights=None, Bcp_init=None, Bcp_init_scale=1,
                  device='cpu', softplus_kwargs=None):
-        """(hierarchical…py:215-290; same arguments, attributes and RNG draws)."""
-        self.X = torch.as_tensor(X, dtype=torch.float32).to(device)
-        self.y = torch.as_tensor(y, dtype=torch.long).to(device)
-        if weights is None:
-            self.weights = torch.ones((rank), device=device)
-        else:
-            self.weights = torch.tensor(weights)
-        if softplus_kwargs is None:
-            self.softplus_kwargs = {'beta': 50, 'threshold': 1}
-        else:
-            self.softplus_kwargs = softplus_kwargs
-        self.rank = rank
-        self.device = device
-        if non_negative is True:
-            self.non_negative = [True] * (self.X.ndim)
-        elif non_negative is False:
-            self.non_negative = [False] * (self.X.ndim)
-        else:
-            self.non_negative = non_negative
-        self.n_classes = len(torch.unique(self.y))
-        B_dims = np.concatenate((np.array(self.X.shape[1:]), [self.n_classes]))
-        if Bcp_init is None:
-            self.Bcp = make_BcpInit(B_dims, self.rank, self.non_negative, scale=Bcp_init_scale, device=self.device)
-        else:
-            self.Bcp = Bcp_init
-        self.loss_running = []
-        self._plan = None
-        self._dev_cache = None
+        """(hierarchical…py:215-290; same arguments, attributes and RNG draws): the multinomial
+        constructor, without a HostStream X and with a class factor that a fit never resizes."""
+        super().__init__(X, y, rank=rank, non_negative=non_negative, weights=weights, Bcp_init=Bcp_init,
+                         Bcp_init_scale=Bcp_init_scale, device=device, softplus_kwargs=softplus_kwargs)
         self._class_factor_auto = False
 
     def _ones(self):
@@ -239,8 +217,6 @@ class CP_logistic_regression(_mnl.CP_logistic_regression):
     def fit(self, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, verbose=False,
             running_loss_logging_interval=10, LBFGS_kwargs=None):
         """LBFGS fit over every factor (hierarchical…py:292-381); closures evaluated on gfx950."""
-        if LBFGS_kwargs is None:
-            raise TypeError("torch.optim.lbfgs.LBFGS() argument after ** must be a mapping, not NoneType")
         return super().fit(lambda_L2=lambda_L2, max_iter=max_iter, tol=tol, patience=patience,
                            weights=self._ones(), verbose=verbose,
                            running_loss_logging_interval=running_loss_logging_interval, LBFGS_kwargs=LBFGS_kwargs)
@@ -268,7 +244,7 @@ class CP_logistic_regression(_mnl.CP_logistic_regression):
         arena = plan.pack(self.Bcp)
         w = self.weights.to(f"cuda:{dev}", torch.float32).contiguous()
         frozen = [0.0] * (plan.n_factors - N_GROUPS)
-        vcb = _Verbose() if verbose == 2 else None
+        vcb = _fit.VerbosePrinter(_fit.line_plain) if verbose == 2 else None
         # the resident route (one workgroup, whole iterations per launch) wherever the plan's envelope
         # admits the problem; plan.describe names the route taken
         resident = plan.set_resident(True)
@@ -278,10 +254,7 @@ class CP_logistic_regression(_mnl.CP_logistic_regression):
             lambda ii: lr_in_force(schedule, ii) + frozen, range(N_GROUPS), verbose_cb=vcb, resident=resident,
             breaks=breaks)
         plan.unpack_into(arena, self.Bcp)
-        if (verbose is True) or (verbose >= 1):
-            print('Convergence reached' if convergence_reached else
-                  'Reached maximum number of iterations without convergence')
-        return convergence_reached
+        return _fit.finish_fit(convergence_reached, verbose)
 
     def predict(self, X=None, y_true=None, Bcp=None, device=None, plot_pref=False):
         """(probabilities, argmax) as numpy (hierarchical…py:473-549; y_true and plot_pref are
@@ -332,12 +305,7 @@ class CP_logistic_regression(_mnl.CP_logistic_regression):
 
     def plot_outputs(self):
         """(hierarchical…py:670-700): unpacks four values from predict's two."""
-        import matplotlib.pyplot as plt
-        plt.figure()
-        plt.plot(self.loss_running)
-        plt.xlabel('logged iteration')
-        plt.ylabel('loss')
-        plt.title('loss')
+        plt = _fit.plot_loss(self.loss_running)
         prob, pred, cm, acc = self.predict()
         fig, axs = plt.subplots(2)
         axs[0].imshow(idx_to_oneHot(pred, self.n_classes), aspect='auto', interpolation='none')

@@ -25,10 +25,9 @@ the spectral fit_Adam / fit stop on a NaN loss.
 Deliberate differences: tensors run on a HIP device, fp32 only; a y with n_out == 1 is
 rejected (the reference broadcasts (N,) + (N,1) to (N,N), Q10).
 """
-import numpy as np
 import torch
 
-from . import _engine, _lib
+from . import _engine, _fit, _lib
 from ._engine import SpectralPlan, adam_hparams, as_device_f32, run_adam_fit
 
 __all__ = ["make_BcpInit", "non_neg_fn", "edge_clamp", "lin_model", "spectral_model", "stepwise_linear_model",
@@ -183,23 +182,6 @@ def stepwise_spectral_model(X, Bcp, weights, non_negative, bias, softplus_kwargs
     return yhat
 
 
-class _VerbosePrinter:
-    """verbose==2 per-iteration print of the reference (spectral…py:728-732), fit-model y_hat."""
-
-    def __init__(self, plan, X, y, weights, norm):
-        self.plan, self.X, self.y, self.w, self.norm = plan, X, y, weights, norm
-        self.var_y = torch.var(y).item()
-        self.grad = torch.zeros(plan.num_grads, dtype=torch.float32, device=X.device)
-        self.yhat = torch.empty_like(y)
-
-    def before_step(self, arena):
-        self.plan.loss_grad(self.X, self.y, None, self.norm, arena, self.w, self.grad, yhat=self.yhat)
-
-    def after_step(self, ii, loss):
-        ratio = torch.var(self.yhat).item() / self.var_y
-        print(f'Iteration: {ii}, Loss: {loss}  ;  Variance ratio (y_hat / y_true): {ratio}')
-
-
 ####################################
 ########### Main class #############
 ####################################
@@ -227,20 +209,12 @@ class CP_linear_regression():
                                       device=device)
         else:
             self.weights = torch.tensor(weights, dtype=self.dtype, requires_grad=False, device=device)
-        if softplus_kwargs is None:
-            self.softplus_kwargs = {'beta': 50, 'threshold': 1}
-        else:
-            self.softplus_kwargs = softplus_kwargs
+        self.softplus_kwargs = _fit.softplus_or_default(softplus_kwargs)
         self.rank_normal = rank_normal
         self.rank_spectral = rank_spectral
         self.rank = rank_normal + rank_spectral
         self.device = device
-        if non_negative is True:
-            self.non_negative = [True] * (len(X_shape))
-        elif non_negative is False:
-            self.non_negative = [False] * (len(X_shape))
-        else:
-            self.non_negative = non_negative
+        self.non_negative = _fit.non_negative_flags(non_negative, len(X_shape))
         self.bias = torch.zeros(y_shape[1:], dtype=self.dtype, requires_grad=True, device=device)
         self.y_shape = y_shape
         B_dims = list(X_shape[1:]) + list(y_shape[1:])
@@ -307,64 +281,39 @@ class CP_linear_regression():
     def _weights(self, dev):
         return self.weights.to(f"cuda:{dev}", torch.float32).contiguous()
 
-    def _set_grads(self, plan, gtot):
-        views = plan.factor_views(gtot)
-        for A, g in zip(list(self.Bcp_n) + list(self.Bcp_c), views):
-            A.grad = g.to(A.device).clone()
-        self.bias.grad = gtot[plan.offsets[6]:].to(self.bias.device).clone().view(self.bias.shape)
-
     # ---- fitting -----------------------------------------------------------------------------
     def fit(self, X, y, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, verbose=False,
             running_loss_logging_interval=10, LBFGS_kwargs=None):
         """LBFGS fit (spectral_tensor_regression.py:541-649): torch.optim.LBFGS drives the
         parameters, every closure evaluation is one gfx950 pass; logs the TOTAL loss (with L2)."""
-        if LBFGS_kwargs is None:
-            raise TypeError("torch.optim.lbfgs.LBFGS() argument after ** must be a mapping, not NoneType")
+        _fit.require_lbfgs_kwargs(LBFGS_kwargs)
         X, y, dev = self._inputs(X, y)
         from .util import HostStream
         if isinstance(X, HostStream):
             raise NotImplementedError("the LBFGS fit needs X resident on the device (use fit_Adam for a HostStream)")
         N, O = X.shape[0], y.shape[1]
         plan = self._get_plan(X, N)
-        optimizer = torch.optim.LBFGS(list(self.Bcp_n) + list(self.Bcp_c) + [self.bias], **LBFGS_kwargs)
         w = self._weights(dev)
-        opts = dict(dtype=torch.float32, device=f"cuda:{dev}")
-        grad = torch.zeros(plan.num_grads, **opts)
-        gtot = torch.zeros(plan.num_params, **opts)
-        loss_out = torch.zeros(1, **opts)
+        grad, gtot, loss_out = _fit.lbfgs_buffers(plan, dev)
         norm = float(N * O)
+        factors = list(self.Bcp_n) + list(self.Bcp_c)
 
-        def total_loss(with_grads):
+        def total_loss(with_grads=True):
             arena = self._arena(plan)
             plan.loss_grad(X, y, None, norm, arena, w, grad)
             plan.finalize_grad(arena, grad, lambda_L2, gtot, loss_out)
             if with_grads:
-                self._set_grads(plan, gtot)
+                _fit.set_factor_grads(plan, gtot, factors, self.bias)
             return loss_out[0].clone()
 
-        def closure():
-            optimizer.zero_grad()
-            return total_loss(True)
+        def log_loss(ii):
+            loss = total_loss(False).item()
+            return loss, (_fit.line_plain(ii, loss) if verbose == 2 else None)
 
-        convergence_reached = False
-        for ii in range(max_iter):
-            if ii % running_loss_logging_interval == 0:
-                self.loss_running.append(total_loss(False).item())
-                if verbose == 2:
-                    print(f'Iteration: {ii}, Loss: {self.loss_running[-1]}')
-            if len(self.loss_running) > patience:
-                if np.sum(np.abs(np.diff(self.loss_running[-patience + 1:]))) < tol:
-                    convergence_reached = True
-                    break
-            elif np.isnan(self.loss_running[-1]):
-                convergence_reached = False
-                print('Loss is NaN. Stopping.')
-                break
-            optimizer.step(closure)
-        if (verbose is True) or (verbose >= 1):
-            print('Convergence reached' if convergence_reached else
-                  'Reached maximum number of iterations without convergence')
-        return convergence_reached
+        return _fit.lbfgs_fit(factors + [self.bias], LBFGS_kwargs, total_loss, log_loss, stop="length",
+                              max_iter=max_iter, tol=tol, patience=patience,
+                              running_loss_logging_interval=running_loss_logging_interval, verbose=verbose,
+                              loss_running=self.loss_running)
 
     def fit_Adam(self, X, y, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, verbose=False,
                  plotting_interval=100, Adam_kwargs=None, process_group=None):
@@ -381,28 +330,18 @@ class CP_linear_regression():
             if verbose in (2, 3) and isinstance(Xd, HostStream):
                 raise NotImplementedError("verbose=2/3 (per-iteration y_hat variance) is not offered for a HostStream X")
             return Xd, yd, dev, self._get_plan(Xd, Xd.shape[0])
-        # under a process group one collective settles the start (_engine.fit_start): a rank-local
-        # failure raises on every rank, the arena sizes agree, and the global sample count
-        if process_group is None:
-            X, y, dev, plan = prepare()
-            n_global = float(X.shape[0])
-        else:
-            (X, y, dev, plan), n_global = _engine.fit_start(process_group, prepare, lambda o: o[0].shape[0],
-                                                            lambda o: o[3].num_params)
+        (X, y, dev, plan), n_global = _fit.start_adam(process_group, prepare, lambda o: float(o[0].shape[0]),
+                                                      lambda o: o[3])
         norm = n_global * y.shape[1]
         arena = self._arena(plan)
         w = self._weights(dev)
-        vcb = _VerbosePrinter(plan, X, y, w, norm) if verbose in (2, 3) else None
+        vcb = _fit.VerbosePrinter(_fit.line_with_ratio, y, _fit.yhat_from_loss_grad(plan, X, y, norm, w)) \
+            if verbose in (2, 3) else None
         convergence_reached, _ = run_adam_fit(plan, X, y, None, norm, arena, w, lambda_L2, max_iter, tol, patience,
                                               hp, self.loss_running, verbose_cb=vcb, process_group=process_group,
                                               arena_checked=True)
         plan.unpack_into(arena, self.Bcp_n, self.Bcp_c, self.bias)
-        if plan.last_stop < 0:
-            print('Loss is NaN. Stopping.')
-        if (verbose is True) or (verbose >= 1):
-            print('Convergence reached' if convergence_reached else
-                  'Reached maximum number of iterations without convergence')
-        return convergence_reached
+        return _fit.finish_fit(convergence_reached, verbose, nan_stopped=plan.last_stop < 0)
 
     ####################################
     ############ POST-HOC ##############
@@ -491,12 +430,7 @@ class CP_linear_regression():
         print('loss_running:', self.loss_running)
 
     def plot_outputs(self):
-        import matplotlib.pyplot as plt
-        plt.figure()
-        plt.plot(self.loss_running)
-        plt.xlabel('logged iteration')
-        plt.ylabel('loss')
-        plt.title('loss')
+        plt = _fit.plot_loss(self.loss_running)
         Bcp_n_final, Bcp_c_final = self.return_Bcp_final()
         if self.rank_normal > 0:
             fig_n, axs = plt.subplots(len(Bcp_n_final))

@@ -17,10 +17,9 @@ Differences from the reference (all deliberate):
 """
 import types
 
-import numpy as np
 import torch
 
-from . import _engine, _lib, _many
+from . import _engine, _fit, _lib, _many
 from ._engine import Plan, as_device_f32, adam_hparams, run_adam_fit
 
 __all__ = ["make_BcpInit", "non_neg_fn", "lin_model", "stepwise_model", "L2_penalty",
@@ -117,22 +116,6 @@ def L2_penalty(B_cp):
     return ii
 
 
-class _VerbosePrinter:
-    """verbose==2 per-iteration print of the reference (standard…py:465-466)."""
-
-    def __init__(self, plan, X, y, weights):
-        self.plan, self.X, self.weights = plan, X, weights
-        self.var_y = torch.var(y).item()
-        self.yhat = None
-
-    def before_step(self, arena):
-        self.yhat = self.plan.forward(self.X, arena, self.weights)
-
-    def after_step(self, ii, loss):
-        ratio = torch.var(self.yhat).item() / self.var_y
-        print(f'Iteration: {ii}, Loss: {loss}  ;  Variance ratio (y_hat / y_true): {ratio}')
-
-
 ####################################
 ########### Main class #############
 ####################################
@@ -156,18 +139,10 @@ class CP_linear_regression():
             self.weights = torch.ones((rank), dtype=self.dtype, requires_grad=False, device=device)
         else:
             self.weights = torch.tensor(weights, dtype=self.dtype, requires_grad=False, device=device)
-        if softplus_kwargs is None:
-            self.softplus_kwargs = {'beta': 50, 'threshold': 1}
-        else:
-            self.softplus_kwargs = softplus_kwargs
+        self.softplus_kwargs = _fit.softplus_or_default(softplus_kwargs)
         self.rank = rank
         self.device = device
-        if non_negative is True:
-            self.non_negative = [True] * (len(X_shape))
-        elif non_negative is False:
-            self.non_negative = [False] * (len(X_shape))
-        else:
-            self.non_negative = non_negative
+        self.non_negative = _fit.non_negative_flags(non_negative, len(X_shape))
         self.bias = torch.tensor([bias_init], dtype=self.dtype, requires_grad=True, device=device)
         B_dims = list(X_shape[1:])
         if Bcp_init is None:
@@ -229,52 +204,33 @@ class CP_linear_regression():
             running_loss_logging_interval=10, LBFGS_kwargs=None):
         """LBFGS fit (standard_tensor_regression.py:305-398).  torch.optim.LBFGS drives the
         parameters; every closure evaluation is one gfx950 loss+gradient pass."""
-        if LBFGS_kwargs is None:
-            raise TypeError("torch.optim.lbfgs.LBFGS() argument after ** must be a mapping, not NoneType")
+        _fit.require_lbfgs_kwargs(LBFGS_kwargs)
         X, y, dev = self._inputs(X, y)
         from .util import HostStream
         if isinstance(X, HostStream):
             raise NotImplementedError("the LBFGS fit needs X resident on the device (use fit_Adam for a HostStream)")
         N = X.shape[0]
         plan = self._get_plan(X, N)
-        params = self.Bcp + [self.bias]
-        optimizer = torch.optim.LBFGS(params, **LBFGS_kwargs)
         w = self.weights.to(f"cuda:{dev}", self.dtype).contiguous()
-        opts = dict(dtype=self.dtype, device=f"cuda:{dev}")
-        grad = torch.zeros(plan.num_grads, **opts)
-        gtot = torch.zeros(plan.num_params, **opts)
-        loss_out = torch.zeros(1, **opts)
+        grad, gtot, loss_out = _fit.lbfgs_buffers(plan, dev, self.dtype)
+        var_y = torch.var(y).item() if verbose == 2 else None
 
-        def closure():
-            optimizer.zero_grad()
+        def closure_loss():
             arena = plan.pack(self.Bcp, self.bias)
             plan.loss_grad_checked(X, y, None, float(N), arena, w, grad)
             plan.finalize_grad(arena, grad, lambda_L2, gtot, loss_out)
-            views = plan.factor_views(gtot)
-            for A, g in zip(self.Bcp, views):
-                A.grad = g.to(A.device).clone()
-            self.bias.grad = gtot[plan.offsets[-1]:].to(self.bias.device).clone().view(self.bias.shape)
+            _fit.set_factor_grads(plan, gtot, self.Bcp, self.bias)
             return loss_out[0].clone()
 
-        convergence_reached = False
-        for ii in range(max_iter):
-            if ii % running_loss_logging_interval == 0:
-                arena = plan.pack(self.Bcp, self.bias)
-                y_hat = plan.forward(X, arena, w)
-                self.loss_running.append(torch.mean((y_hat - y) ** 2).item())
-                if verbose == 2:
-                    print(f'Iteration: {ii}, Loss: {self.loss_running[-1]}  ;  Variance ratio (y_hat / y_true): '
-                          f'{torch.var(y_hat).item() / torch.var(y).item()}')
-            if ii > patience:
-                if np.sum(np.abs(np.diff(self.loss_running[ii - patience:]))) < tol:
-                    convergence_reached = True
-                    break
-            optimizer.step(closure)
-        plan.check_status()
-        if (verbose is True) or (verbose >= 1):
-            print('Convergence reached' if convergence_reached else
-                  'Reached maximum number of iterations without convergence')
-        return convergence_reached
+        def log_loss(ii):  # the data loss of the forward kernel, without the L2 term
+            y_hat = plan.forward(X, plan.pack(self.Bcp, self.bias), w)
+            loss = torch.mean((y_hat - y) ** 2).item()
+            return loss, (_fit.line_with_ratio(ii, loss, torch.var(y_hat).item() / var_y) if verbose == 2 else None)
+
+        return _fit.lbfgs_fit(self.Bcp + [self.bias], LBFGS_kwargs, closure_loss, log_loss, stop="index",
+                              max_iter=max_iter, tol=tol, patience=patience,
+                              running_loss_logging_interval=running_loss_logging_interval, verbose=verbose,
+                              loss_running=self.loss_running, after=plan.check_status)
 
     def fit_Adam(self, X, y, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, verbose=False,
                  Adam_kwargs=None, process_group=None):
@@ -293,25 +249,16 @@ class CP_linear_regression():
             if verbose == 2 and isinstance(Xd, HostStream):
                 raise NotImplementedError("verbose=2 (per-iteration y_hat variance) is not offered for a HostStream X")
             return Xd, yd, dev, self._get_plan(Xd, Xd.shape[0])
-        # under a process group one collective settles the start (_engine.fit_start): a rank-local
-        # failure raises on every rank, the arena sizes agree, and the global sample count
-        if process_group is None:
-            X, y, dev, plan = prepare()
-            n_global = float(X.shape[0])
-        else:
-            (X, y, dev, plan), n_global = _engine.fit_start(process_group, prepare, lambda o: o[0].shape[0],
-                                                            lambda o: o[3].num_params)
+        (X, y, dev, plan), n_global = _fit.start_adam(process_group, prepare, lambda o: float(o[0].shape[0]),
+                                                      lambda o: o[3])
         arena = plan.pack(self.Bcp, self.bias)
         w = self.weights.to(f"cuda:{dev}", self.dtype).contiguous()
-        vcb = _VerbosePrinter(plan, X, y, w) if verbose == 2 else None
+        vcb = _fit.VerbosePrinter(_fit.line_with_ratio, y, lambda a: plan.forward(X, a, w)) if verbose == 2 else None
         convergence_reached, _ = run_adam_fit(plan, X, y, None, n_global, arena, w, lambda_L2, max_iter, tol,
                                               patience, hp, self.loss_running, verbose_cb=vcb,
                                               process_group=process_group, arena_checked=True)
         plan.unpack_into(arena, self.Bcp, self.bias)
-        if (verbose is True) or (verbose >= 1):
-            print('Convergence reached' if convergence_reached else
-                  'Reached maximum number of iterations without convergence')
-        return convergence_reached
+        return _fit.finish_fit(convergence_reached, verbose)
 
     ####################################
     ############ POST-HOC ##############
@@ -322,18 +269,7 @@ class CP_linear_regression():
         like the reference (quirk Q12)."""
         if device is None:
             device = self.device
-        if isinstance(X, torch.Tensor) is False:
-            X = torch.tensor(X, dtype=torch.float32, requires_grad=False).to(device)
-        elif X.device != torch.device(device):
-            X = X.to(device)
-        if Bcp is None:
-            Bcp = self.Bcp
-        elif isinstance(Bcp[0], torch.Tensor) is False:
-            for ii in range(len(Bcp)):
-                Bcp[ii] = torch.tensor(Bcp[ii], dtype=torch.float32, requires_grad=False).to(device)
-        elif Bcp[0].device != torch.device(device):
-            for ii in range(len(Bcp)):
-                Bcp[ii] = Bcp[ii].to(device)
+        X, Bcp = _fit.coerce_predict_inputs(X, Bcp, self.Bcp, device)
         y_hat = lin_model(X, Bcp, self.weights, self.non_negative, self.bias,
                           softplus_kwargs=self.softplus_kwargs).detach().cpu().numpy()
         return y_hat
@@ -376,12 +312,7 @@ class CP_linear_regression():
         print('loss_running:', self.loss_running)
 
     def plot_outputs(self):
-        import matplotlib.pyplot as plt
-        plt.figure()
-        plt.plot(self.loss_running)
-        plt.xlabel('logged iteration')
-        plt.ylabel('loss')
-        plt.title('loss')
+        plt = _fit.plot_loss(self.loss_running)
         Bcp_final = self.return_Bcp_final()
         fig, axs = plt.subplots(len(Bcp_final))
         for ii, val in enumerate(Bcp_final):

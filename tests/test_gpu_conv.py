@@ -328,3 +328,27 @@ def test_verbose_prints_variance_ratio(capsys):
                  max_iter=2, tol=0.0, patience=10, verbose=3, Adam_kwargs={'lr': 0.01})
     out = capsys.readouterr().out
     assert out.count("Variance ratio (y_hat / y_true)") == 2 and "Iteration: 1, Loss:" in out
+
+
+def test_lbfgs_verbose_lines_and_nan_stop(capsys):
+    """fit's per-iteration line (verbose=3: the logged loss and the variance ratio), its convergence
+    line, and its NaN notice: a NaN target makes the first logged loss NaN and the fit stops there."""
+    d = cr.load("cvs_base")
+    m = d["meta"]
+    X, y = torch.tensor(d["X"], device=DEV), torch.tensor(d["y"], device=DEV)
+    lbfgs = {'lr': 1, 'max_iter': 2}
+    mod = _model_from(d)
+    conv = mod.fit(X, y, lambda_L2=cr.lam3(m), max_iter=2, tol=0.0, verbose=3, running_loss_logging_interval=1,
+                   LBFGS_kwargs=lbfgs)
+    assert conv is False and len(mod.loss_running) == 2
+    lines = capsys.readouterr().out.splitlines()
+    for ii, loss in enumerate(mod.loss_running):
+        head = f'Iteration: {ii}, Loss: {loss}  ;  Variance ratio (y_hat / y_true): '
+        assert lines[ii].startswith(head) and float(lines[ii][len(head):]) > 0, lines[ii]
+    assert lines[2:] == ["Reached maximum number of iterations without convergence"]
+    y[50, 1] = float("nan")
+    mod = _model_from(d)
+    conv = mod.fit(X, y, lambda_L2=cr.lam3(m), max_iter=3, tol=0.0, running_loss_logging_interval=1,
+                   LBFGS_kwargs=lbfgs)
+    assert conv is False and len(mod.loss_running) == 1 and np.isnan(mod.loss_running[0])
+    assert capsys.readouterr().out == "Loss is NaN. Stopping.\n"

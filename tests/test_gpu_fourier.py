@@ -456,3 +456,31 @@ def test_envelope_describe_and_call_order():
         torch.cuda.synchronize()
     finally:
         assert lib.tr_plan_destroy(h) == 0
+
+
+def test_lbfgs_verbose_lines_and_nan_stops(capsys):
+    """fit's per-iteration line (verbose=2: the logged loss and the variance ratio, five significant
+    digits each), its convergence line, and the NaN notice of both fits: a NaN target makes the first
+    logged loss NaN and either fit stops there."""
+    d = fr.load("cfs_lbfgs")
+    m = d["meta"]
+    X, y = torch.tensor(d["X"], device=DEV), torch.tensor(d["y"], device=DEV)
+    kw = dict(_fit_kwargs(m), lambda_L2=m["lambda_L2"], tol=0.0)
+    lbfgs = dict(running_loss_logging_interval=1, LBFGS_kwargs=dict(m["lbfgs_kwargs"]))
+    mod = _model_from(d)
+    conv = mod.fit(X, y, **dict(kw, max_iter=2), verbose=2, **lbfgs)
+    assert conv is False and len(mod.loss_running) == 2
+    lines = capsys.readouterr().out.splitlines()
+    for ii, loss in enumerate(mod.loss_running):
+        head = f'Iter: {ii}, loss: {loss:.5}, var_ratio (y_hat/y_true): '
+        assert lines[ii].startswith(head) and float(lines[ii][len(head):]) > 0, lines[ii]
+    assert lines[2:] == ["Reached maximum number of iterations without convergence"]
+    y[50, 1] = float("nan")
+    for adam in (False, True):
+        mod = _model_from(d)
+        if adam:
+            conv = mod.fit_Adam(X, y, **dict(kw, max_iter=3), Adam_kwargs={'lr': 0.01})
+        else:
+            conv = mod.fit(X, y, **dict(kw, max_iter=3), **lbfgs)
+        assert conv is False and len(mod.loss_running) == 1 and np.isnan(mod.loss_running[0])
+        assert capsys.readouterr().out == "Loss is NaN. Stopping.\n"

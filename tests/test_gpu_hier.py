@@ -622,3 +622,21 @@ def test_resident_envelope_and_arguments():
     with pytest.raises(ValueError):  # more rows than the plan was made for
         p.fit_resident(torch.zeros(41, 8, 12, device=DEV), y, z, w, z.clone(), z.clone(), None, 0.0, hp, [0.01] * 3, 1,
                        1, hist, 0, 0, 10, 0.0, stop)
+
+
+def test_verbose_lines_of_both_fits(capsys):
+    """verbose=2 of fit and fit_Adam: 'Iteration: i, Loss: l' per logged iteration with the logged
+    loss, then the convergence line."""
+    d = fixture("hier_lbfgs")
+    m = d["meta"]
+    for adam in (False, True):
+        mm = new_model(d)
+        if adam:
+            conv = mm.fit_Adam(lambda_L2=m["lambda_L2"], max_iter=2, tol=0.0, verbose=2, Adam_kwargs={'lr': 0.01})
+        else:
+            conv = mm.fit(lambda_L2=m["lambda_L2"], max_iter=2, tol=0.0, verbose=2, running_loss_logging_interval=1,
+                          LBFGS_kwargs=m["lbfgs_kwargs"])
+        assert conv is False and len(mm.loss_running) == 2
+        assert capsys.readouterr().out.splitlines() == [
+            f'Iteration: {ii}, Loss: {loss}' for ii, loss in enumerate(mm.loss_running)] + [
+            "Reached maximum number of iterations without convergence"]

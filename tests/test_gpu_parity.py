@@ -1177,3 +1177,57 @@ def test_mttkrp3_matches_general_kernel(shape, rank, nonneg, monkeypatch):
         print("  vs fp64: new", e_new, "general", e_old)
         for a, b in zip(e_new, e_old):
             assert a <= 1.5 * b + 2e-8, (e_new, e_old)
+
+
+def _ratio_lines(out, losses):
+    """The 'Iteration: i, Loss: l  ;  Variance ratio (y_hat / y_true): r' lines of `out`, one per loss;
+    returns what follows them."""
+    lines = out.splitlines()
+    for ii, loss in enumerate(losses):
+        head = f'Iteration: {ii}, Loss: {loss}  ;  Variance ratio (y_hat / y_true): '
+        assert lines[ii].startswith(head), (lines[ii], head)
+        assert np.isfinite(float(lines[ii][len(head):])) and float(lines[ii][len(head):]) > 0
+    return lines[len(losses):]
+
+
+def test_linear_verbose_lines(capsys):
+    """verbose=2 of fit and fit_Adam: one line per logged iteration with the logged loss and the
+    variance ratio, then the convergence line."""
+    from tensor_regression_amd import CP_linear_regression
+    d = load("lin_lbfgs")
+    m = d["meta"]
+    X, y = d["X"].to(DEV), torch.tensor(d["y"], device=DEV)
+    for adam in (False, True):
+        Bcp = [torch.tensor(a, device=DEV).requires_grad_(True) for a in d["Bcp0_list"]]
+        model = CP_linear_regression(X.shape, rank=m["rank"], Bcp_init=Bcp, device=DEV)
+        if adam:
+            conv = model.fit_Adam(X, y, lambda_L2=m["lambda_L2"], max_iter=2, tol=0.0, verbose=2,
+                                  Adam_kwargs={'lr': 0.01})
+        else:
+            conv = model.fit(X, y, lambda_L2=m["lambda_L2"], max_iter=2, tol=0.0, verbose=2,
+                             running_loss_logging_interval=1, LBFGS_kwargs=m["lbfgs_kwargs"])
+        assert conv is False and len(model.loss_running) == 2
+        rest = _ratio_lines(capsys.readouterr().out, model.loss_running)
+        assert rest == ["Reached maximum number of iterations without convergence"]
+
+
+def test_multinomial_verbose_lines(capsys):
+    """verbose=2 of fit and fit_Adam: 'Iteration: i, Loss: l' per logged iteration, then the
+    convergence line; verbose=1 prints the convergence line alone."""
+    from tensor_regression_amd import CP_logistic_regression
+    d = load(names("mnllbfgs_")[0])
+    m = d["meta"]
+    cw = np.array(m["class_weights"])
+    for adam, verbose in ((False, 2), (True, 2), (True, 1)):
+        Bcp = [torch.tensor(a, device=DEV).requires_grad_(True) for a in d["Bcp0_list"]]
+        mm = CP_logistic_regression(d["X"].numpy(), d["y"], rank=m["rank"], Bcp_init=Bcp, device=DEV)
+        if adam:
+            conv = mm.fit_Adam(lambda_L2=m["lambda_L2"], max_iter=2, tol=0.0, weights=cw, verbose=verbose,
+                               Adam_kwargs={'lr': 0.01})
+        else:
+            conv = mm.fit(lambda_L2=m["lambda_L2"], max_iter=2, tol=0.0, weights=cw, verbose=verbose,
+                          running_loss_logging_interval=1, LBFGS_kwargs=m["lbfgs_kwargs"])
+        assert conv is False and len(mm.loss_running) == 2
+        want = [f'Iteration: {ii}, Loss: {loss}' for ii, loss in enumerate(mm.loss_running)] if verbose == 2 else []
+        assert capsys.readouterr().out.splitlines() == want + [
+            "Reached maximum number of iterations without convergence"]

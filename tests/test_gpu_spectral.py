@@ -420,3 +420,40 @@ def test_spectral_envelope_errors():
     with pytest.raises(NotImplementedError):
         m.fit_Adam(torch.zeros(4, 8, 5, device=DEV), torch.zeros(4, 1, device=DEV), max_iter=1,
                    Adam_kwargs={'lr': 0.01})
+
+
+def test_spectral_verbose_lines_and_nan_stop(capsys):
+    """What the two fits print: fit's 'Iteration: i, Loss: l' (verbose=2), fit_Adam's line with the
+    variance ratio (verbose=2 and 3), the convergence line, and the NaN notice of both (a NaN target
+    makes the first logged loss NaN: both stop there, not converged, whatever `verbose` says)."""
+    d = load_spectral("spec_lbfgs")
+    m = d["meta"]
+    X, y = d["X"].to(DEV), torch.tensor(d["y"], device=DEV)
+    last = "Reached maximum number of iterations without convergence"
+    model = _model_from(d)
+    conv = model.fit(X, y, lambda_L2=m["lambda_L2"], max_iter=2, tol=0.0, verbose=2,
+                     running_loss_logging_interval=1, LBFGS_kwargs=m["lbfgs_kwargs"])
+    assert conv is False and len(model.loss_running) == 2
+    assert capsys.readouterr().out.splitlines() == [
+        f'Iteration: {ii}, Loss: {loss}' for ii, loss in enumerate(model.loss_running)] + [last]
+    for verbose in (2, 3):
+        model = _model_from(d)
+        conv = model.fit_Adam(X, y, lambda_L2=m["lambda_L2"], max_iter=2, tol=0.0, verbose=verbose,
+                              Adam_kwargs={'lr': 0.01})
+        assert conv is False and len(model.loss_running) == 2
+        lines = capsys.readouterr().out.splitlines()
+        for ii, loss in enumerate(model.loss_running):
+            head = f'Iteration: {ii}, Loss: {loss}  ;  Variance ratio (y_hat / y_true): '
+            assert lines[ii].startswith(head) and float(lines[ii][len(head):]) > 0, lines[ii]
+        assert lines[2:] == [last]
+    y_nan = y.clone()
+    y_nan[0, 0] = float("nan")
+    for adam in (False, True):
+        model = _model_from(d)
+        if adam:
+            conv = model.fit_Adam(X, y_nan, lambda_L2=m["lambda_L2"], max_iter=3, tol=0.0, Adam_kwargs={'lr': 0.01})
+        else:
+            conv = model.fit(X, y_nan, lambda_L2=m["lambda_L2"], max_iter=3, tol=0.0,
+                             running_loss_logging_interval=1, LBFGS_kwargs=m["lbfgs_kwargs"])
+        assert conv is False and len(model.loss_running) == 1 and np.isnan(model.loss_running[0])
+        assert capsys.readouterr().out == "Loss is NaN. Stopping.\n"
