@@ -467,6 +467,78 @@ int tr_linear_many_fit(int device, const float* X, int64_t n_rows, int64_t x_row
                        void* table_host, void* table_dev, int64_t table_bytes, void* stream);
 
 /*
+ * Shared-X multinomial sweep: CP multinomial models with two feature modes and a class factor (a
+ * hyperparameter grid: one model per grid point) fitted over ONE X (n_rows, I0, I1) float32 at
+ * x_row_stride floats (0 = I0 * I1; a stride below I0 * I1 is a windowed view).  No plan is involved.
+ * A member with C classes is C columns of a dense coefficient matrix; the members of a call hold at
+ * most 64 columns in total (four 16-column MFMA tiles: 12 members at C = 5, 4 at C = 16).  Member j
+ * owns the columns col0_j .. col0_j + C_j - 1, col0 the running sum of the class counts.  The forward
+ * passes are one skinny GEMM over X and the gradient passes another, so an iteration reads X twice
+ * whatever the number of members, and the number of kernel launches per iteration (9) does not depend
+ * on it either.  Members differ in labels, class count, rank, nonneg[3], softplus settings, CP
+ * weights, class weights, lambda and every optimizer setting.
+ * The loss is the module's: CrossEntropyLoss(weight) on the softmax output (the double softmax),
+ * sum_n cw[y_n] l_n / cw_norm with cw_norm = sum_n cw[y_n].
+ * The envelope: P = I0 * I1 and the row stride multiples of 4 floats, X 16-byte aligned, n_classes
+ * 2..16, rank 1..32, I0, I1 <= 2^20, P <= 2^28; any n_rows >= 1.
+ * A member's `params` is its plan arena (factor 0, factor 1, class factor), `grad` its gradient arena
+ * of (I0 + I1 + n_classes) * rank + 2 floats, laid out as tr_loss_grad leaves it (factor gradients,
+ * data loss, status).  The Adam, history and stop fields are those of tr_linear_member.  A member
+ * whose *stop_flag is nonzero or whose n_iters is used up is left untouched: parameters, Adam state
+ * and loss history (its grad arena is scratch).
+ * No floating-point atomics and fixed summation orders that depend on (n_rows, I0, I1) alone: a
+ * member's results are bitwise reproducible and depend neither on the other members, nor on its
+ * columns' position, nor on the number of tiles in use.  Given the same gradient bits the update is
+ * tr_adam_step's, bit for bit.
+ *   tr_mnl_many_envelope           1 inside the envelope, 0 outside; needs no device
+ *   tr_mnl_many_workspace_bytes    size of the caller's device workspace (<= 0: outside the envelope)
+ *   tr_mnl_many_member_table_bytes size of the argument table for n_members
+ *   tr_mnl_many_loss_grad          one evaluation: fills every member's grad arena
+ *   tr_mnl_many_step               the update of every member with n_iters = 1 from its grad arena
+ *   tr_mnl_many_fit                max(n_iters) iterations of both
+ * Every entry checks the shape and EVERY member before any device call (NULL buffer, n_iters out of
+ * range, step < 1, iter or hist_base < 0, lr < 0, cw_norm <= 0, amsgrad without max_exp_avg_sq, more
+ * than 64 columns in total: TR_E_ARG; outside the envelope: TR_E_UNSUPPORTED; tr_last_error() names
+ * the member's index) and launches nothing if one fails.  n_members == 0 succeeds.  table_host
+ * (pinned) and table_dev as in tr_fit_adam_resident_many.
+ */
+typedef struct tr_mnl_many_member {
+  float* params;              /* (I0 + I1 + n_classes) * rank: factor 0, factor 1, class factor */
+  const float* weights;       /* [rank] CP component weights */
+  const int64_t* y;           /* [n_rows] labels in 0..n_classes-1 */
+  const float* class_weights; /* [n_classes] */
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* max_exp_avg_sq;      /* amsgrad only, else may be NULL */
+  float* grad;                /* (I0 + I1 + n_classes) * rank + 2 */
+  double* loss_hist;
+  int32_t* stop_flag;
+  double cw_norm;             /* sum_n class_weights[y_n] */
+  int32_t n_classes, rank;
+  int32_t nonneg[3];
+  int32_t amsgrad;
+  float softplus_beta, softplus_threshold;
+  float lambda_l2;
+  int32_t n_iters;
+  double lr, beta1, beta2, eps, weight_decay;
+  int64_t step, hist_base, iter, patience;
+  double tol;
+} tr_mnl_many_member;
+
+int tr_mnl_many_envelope(int64_t I0, int64_t I1, int64_t x_row_stride, int n_classes, int rank);
+int64_t tr_mnl_many_workspace_bytes(int64_t n_rows, int64_t I0, int64_t I1);
+int64_t tr_mnl_many_member_table_bytes(int n_members);
+int tr_mnl_many_loss_grad(int device, const float* X, int64_t n_rows, int64_t x_row_stride, int64_t I0, int64_t I1,
+                          const tr_mnl_many_member* members, int n_members, void* workspace,
+                          int64_t workspace_bytes, void* table_host, void* table_dev, int64_t table_bytes,
+                          void* stream);
+int tr_mnl_many_step(int device, int64_t I0, int64_t I1, const tr_mnl_many_member* members, int n_members,
+                     void* table_host, void* table_dev, int64_t table_bytes, void* stream);
+int tr_mnl_many_fit(int device, const float* X, int64_t n_rows, int64_t x_row_stride, int64_t I0, int64_t I1,
+                    const tr_mnl_many_member* members, int n_members, void* workspace, int64_t workspace_bytes,
+                    void* table_host, void* table_dev, int64_t table_bytes, void* stream);
+
+/*
  * Fold the NEXT iteration's factor preparation into tr_adam_step: with enable = 1, on a plan
  * that takes the factored multinomial single pass, every tr_adam_step also computes
  * softplus(A_k) and its derivative from the parameters it has just written, and the following

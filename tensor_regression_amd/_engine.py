@@ -1467,6 +1467,91 @@ def run_linear_many(dev, X, members, sync_every=64, trace=None):
     return stops, 2 * sum(chunks)
 
 
+MNL_MANY_MAX_COLS = 64  # columns (classes summed over the members) of one group of the shared-X multinomial sweep
+
+
+def mnl_many_enabled():
+    """TR_MNL_MANY=0 sends every model of the multinomial fit_Adam_many to its own fit_Adam."""
+    return not os.environ.get("TR_MNL_MANY", "").startswith("0")
+
+
+def mnl_many_envelope(I0, I1, x_row_stride, n_classes, rank):
+    """tr_mnl_many_envelope: whether the shared-X multinomial sweep takes this shape (needs no device)."""
+    return bool(_lib.load().tr_mnl_many_envelope(int(I0), int(I1), int(x_row_stride), int(n_classes), int(rank)))
+
+
+class MnlManyBuffers:
+    """What one group of the shared-X multinomial sweep needs on the device beside its members' arrays:
+    the workspace of tr_mnl_many_workspace_bytes and the two table buffers."""
+
+    def __init__(self, dev, N, I0, I1, M):
+        lib = _lib.load()
+        self.dev, self.M = dev, M
+        self.ws_bytes = int(lib.tr_mnl_many_workspace_bytes(N, I0, I1))
+        if self.ws_bytes <= 0:
+            raise ValueError(f"the shared-X multinomial sweep does not take the shape ({N}, {I0}, {I1})")
+        self.table_bytes = int(lib.tr_mnl_many_member_table_bytes(M))
+        with torch.cuda.device(dev):
+            self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=f"cuda:{dev}")
+        self.table_host, self.table_dev = table_buffers(dev, self.table_bytes)
+
+
+def mnl_many_member_array(members, own_state=True):
+    """The (ctypes array, numpy record view of the same memory) of tr_mnl_many_member for `members`:
+    objects with arena, w, y (int64), cw, W, grad, m, v, vmax | None, hist, stop (device tensors),
+    n_classes, rank, nonneg[3], beta, thr, lambda_L2, hp, patience, tol, hist_base.  step / iter /
+    n_iters are the caller's.  own_state=False: as linear_member_array."""
+    arr, rec = member_records(_lib.MnlManyMember, len(members))
+    for r, mb in zip(arr, members):
+        r.params, r.weights, r.y = mb.arena.data_ptr(), mb.w.data_ptr(), mb.y.data_ptr()
+        r.class_weights, r.cw_norm = mb.cw.data_ptr(), float(mb.W)
+        r.n_classes, r.rank, r.lr = int(mb.n_classes), int(mb.rank), mb.hp["lr"]
+        fill_adam_fields(r, mb, mb.hist_base if own_state else len(mb.loss_running))
+        r.step, r.iter, r.n_iters = 1, 0, 0
+        if own_state:
+            r.grad, r.exp_avg, r.exp_avg_sq = mb.grad.data_ptr(), mb.m.data_ptr(), mb.v.data_ptr()
+            r.max_exp_avg_sq = mb.vmax.data_ptr() if mb.vmax is not None else None
+            r.loss_hist, r.stop_flag = mb.hist.data_ptr(), mb.stop.data_ptr()
+    return arr, rec
+
+
+def run_mnl_many(dev, X, members, sync_every=64, trace=None):
+    """Fit CP multinomial models whose class counts sum to at most 64 over one X together
+    (tr_mnl_many_fit): every chunk of up to `sync_every` (<= 64) iterations is one call, 9 kernel
+    launches per iteration whatever the members are, X read twice per iteration.
+
+    X: (N, I0, I1) float32 on cuda:`dev`, samples contiguous, any row stride inside the envelope.
+    `members`: objects with arena (factor 0, factor 1, class factor; float32 on the device), w [R], y [N]
+    int64, cw [C] and W (the class weights and sum_n cw[y_n]), n_classes, rank, nonneg[3], beta, thr
+    (softplus), lambda_L2, hp (adam_hparams), max_iter, tol, patience and loss_running (extended in
+    place).  The loop is _run_many_fit's.  Returns (stop values, X passes): stop > 0 is a plateau after
+    that many iterations.  `trace` (a list, for tools/mnl_many_shapes.py) receives per chunk
+    (iterations, ms between device events around the call)."""
+    lib = _lib.load()
+    M = len(members)
+    if M == 0:
+        return [], 0
+    n_cols = sum(int(mb.n_classes) for mb in members)
+    if n_cols > MNL_MANY_MAX_COLS:
+        raise ValueError(f"run_mnl_many takes at most {MNL_MANY_MAX_COLS} columns, got {n_cols}")
+    N, I0, I1 = (int(d) for d in X.shape)
+    xld = int(X.stride(0)) if N > 1 else I0 * I1
+    bufs = MnlManyBuffers(dev, N, I0, I1, M)
+    arr, rec = mnl_many_member_array(members, own_state=False)
+    stream = stream_handle(dev)
+
+    def call(ii):
+        check(lib.tr_mnl_many_fit(dev, ptr(X), N, xld, I0, I1, arr, M, ptr(bufs.ws), bufs.ws_bytes,
+                                  ptr(bufs.table_host), ptr(bufs.table_dev), bufs.table_bytes, stream),
+              "tr_mnl_many_fit")
+
+    # a member's state: its gradient arena (num_params + 2), then m, v and vmax
+    stops, chunks = _run_many_fit(dev, members, rec, ("grad", "exp_avg", "exp_avg_sq", "max_exp_avg_sq"),
+                                  lambda mb: mb.arena.numel() + 2, call, (), sync_every,
+                                  None if trace is None else lambda n, device_ms, _: trace.append((n, device_ms)))
+    return stops, 2 * sum(chunks)
+
+
 SCORE_ROW_BLOCK = _lib.TR_SCORE_ROW_BLOCK  # rows per workgroup of tr_mnl_score_many
 
 

@@ -62,6 +62,17 @@ class LinearMember(_c.Structure):
                 ("hist_base", _c.c_int64), ("iter", _c.c_int64), ("patience", _c.c_int64), ("tol", _c.c_double)]
 
 
+class MnlManyMember(_c.Structure):
+    """`tr_mnl_many_member`: one member of the tr_mnl_many_* entries (fields in the header's order)."""
+    _fields_ = [("params", _vp), ("weights", _vp), ("y", _vp), ("class_weights", _vp), ("exp_avg", _vp),
+                ("exp_avg_sq", _vp), ("max_exp_avg_sq", _vp), ("grad", _vp), ("loss_hist", _vp), ("stop_flag", _vp),
+                ("cw_norm", _c.c_double), ("n_classes", _c.c_int32), ("rank", _c.c_int32), ("nonneg", _c.c_int32 * 3),
+                ("amsgrad", _c.c_int32), ("softplus_beta", _c.c_float), ("softplus_threshold", _c.c_float),
+                ("lambda_l2", _c.c_float), ("n_iters", _c.c_int32), ("lr", _c.c_double), ("beta1", _c.c_double),
+                ("beta2", _c.c_double), ("eps", _c.c_double), ("weight_decay", _c.c_double), ("step", _c.c_int64),
+                ("hist_base", _c.c_int64), ("iter", _c.c_int64), ("patience", _c.c_int64), ("tol", _c.c_double)]
+
+
 # exported symbol -> (restype, argtypes)
 SIGNATURES = {
     "tr_abi_version": (_c.c_int, []),
@@ -135,6 +146,16 @@ SIGNATURES = {
     "tr_linear_many_fit": (_c.c_int, [_c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
                                       _c.POINTER(LinearMember), _c.c_int, _vp, _c.c_int64, _vp, _vp, _c.c_int64,
                                       _vp]),
+    "tr_mnl_many_envelope": (_c.c_int, [_c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int]),
+    "tr_mnl_many_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int64, _c.c_int64]),
+    "tr_mnl_many_member_table_bytes": (_c.c_int64, [_c.c_int]),
+    "tr_mnl_many_loss_grad": (_c.c_int, [_c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
+                                         _c.POINTER(MnlManyMember), _c.c_int, _vp, _c.c_int64, _vp, _vp, _c.c_int64,
+                                         _vp]),
+    "tr_mnl_many_step": (_c.c_int, [_c.c_int, _c.c_int64, _c.c_int64, _c.POINTER(MnlManyMember), _c.c_int, _vp, _vp,
+                                    _c.c_int64, _vp]),
+    "tr_mnl_many_fit": (_c.c_int, [_c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
+                                   _c.POINTER(MnlManyMember), _c.c_int, _vp, _c.c_int64, _vp, _vp, _c.c_int64, _vp]),
     "tr_plan_set_prepare_next": (_c.c_int, [_vp, _c.c_int]),
     "tr_plan_create_f64": (_c.c_int, [_c.POINTER(_vp), _c.c_int, _c.c_int, _c.POINTER(_c.c_int64), _c.c_int,
                                       _c.c_int64, _c.POINTER(_c.c_int32), _c.c_double, _c.c_double]),

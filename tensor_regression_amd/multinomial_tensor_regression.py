@@ -7,6 +7,8 @@ log-softmax to them again, multinomial_tensor_regression.py:180-187 + :448-450) 
 hot path (factor prep, X·B over all classes, softmax, weighted CE, X^T·dZ, MTTKRP, Adam)
 running as gfx950 HIP kernels through the C ABI.
 """
+import types
+
 import numpy as np
 import torch
 
@@ -15,7 +17,7 @@ from ._engine import Plan, as_device_f32, adam_hparams, run_adam_fit
 from .standard_tensor_regression import _plan_for, L2_penalty  # noqa: F401  (L2_penalty re-exported)
 
 __all__ = ["squeeze_integers", "confusion_matrix", "idx_to_oneHot", "make_BcpInit", "non_neg_fn", "model",
-           "L2_penalty", "CP_logistic_regression", "predict_many", "score_many"]
+           "L2_penalty", "CP_logistic_regression", "predict_many", "score_many", "fit_Adam_many"]
 
 
 ####################################
@@ -670,3 +672,148 @@ def score_many(models, X=None, y_true=None, weights=None, report=None):
             results.append({"loss": lsum / wsum, "acc": float(np.trace(counts) / e.N), "counts": counts,
                             "cm": counts / np.sum(counts, axis=0)[None, :]})
     return _many.finish_many(results, False, report, batched=batched, alone=alone, launches=1 if batched else 0)
+
+
+####################################
+####### Many models, one X #########
+####################################
+
+# The smallest group the shared-X sweep takes, by the largest class count in the group: a group reads X
+# twice per iteration and runs its GEMMs in exact fp32 on the matrix cores, a model alone reads X once
+# where its single-pass kernel applies.  Measured against the loop of fit_Adam calls (tools/
+# mnl_many_shapes.py, DESIGN.md "Shared-X multinomial sweep"); per class count the smallest measured M
+# that beats the loop at every measured shape by more than the spreads, an unmeasured class count takes
+# the threshold of the next larger measured one, and None keeps a class count with the loop.  From
+# profiles/mnl_many_shapes.txt (ms per iteration, group against loop):
+#   C = 5   M = 1: 0.958 / 1.304 (line 7, the notebook shape) but 0.837 / 0.423 (line 16, config 3's shape);
+#           M = 2: 0.827 / 0.811 (line 17) loses; M = 3: 1.036 / 3.882 (line 9) and 0.846 / 1.192 (line 18)   -> 3
+#   C = 10  M = 2: 1.034 / 0.814 (line 12) loses; M = 3: 1.063 / 1.186 (line 13), spreads 0.006 + 0.036  -> 3
+#   C = 16  M = 4: 2.183 / 10.251 (line 15, the notebook shape) but 1.758 / 1.606 (line 22, config 3's
+#           shape): never ahead at every measured shape                                                 -> None
+MNL_MANY_MIN_BATCH = {5: 3, 10: 3, 16: None}
+
+
+def mnl_many_min_batch(n_classes):
+    """The default minimum group size for a group whose largest class count is `n_classes` (None: the
+    loop of fit_Adam calls is never slower; such a group is formed only with an explicit min_batch)."""
+    for C in sorted(MNL_MANY_MIN_BATCH):
+        if n_classes <= C:
+            return MNL_MANY_MIN_BATCH[C]
+    return None
+
+
+def _x_key(Xd):
+    """Two models share a stream when their device X is the same storage seen the same way."""
+    return (Xd.data_ptr(), tuple(Xd.shape), tuple(Xd.stride()), Xd.dtype, str(Xd.device))
+
+
+def fit_Adam_many(models, lambda_L2=0.01, max_iter=1000, tol=1e-5, patience=10, weights=None, verbose=False,
+                  Adam_kwargs=None, min_batch=None, report=None):
+    """fit_Adam of many CP_logistic_regression models that share ONE X: the outer loop of a
+    hyperparameter grid (demo_MultinomialTensorRegression.ipynb: a fresh model per grid point, every
+    model on the same X) with X streamed twice per iteration for a whole group of models instead of
+    once per model.
+
+    models: CP_logistic_regression objects of this module, each with its own y, class count, rank,
+    non_negative, softplus_kwargs, CP weights, initial Bcp and loss_running.  lambda_L2, max_iter, tol,
+    patience, weights (class weights, as in fit_Adam) and Adam_kwargs are each one value for all models
+    or a list of len(models) values.  Afterwards every model is in the state its own `fit_Adam(...)`
+    would have left it, up to fp32 summation order (Bcp, loss_running extended, plateau stops included);
+    `model._plan` is untouched.  The returned list holds each model's convergence_reached.
+
+    Models whose device X is the same storage (data pointer, shape, strides, dtype) share a stream:
+    that is what happens when every model was built from one float32 device tensor.  Building each
+    model from a numpy X uploads a private copy per model, and those models do not group.  Within one
+    X, groups are filled in list order while the class counts sum to at most 64 columns (12 models at
+    5 classes); labels and class counts may differ per model.  The envelope: float32, 3-D X, 2..16
+    classes, rank <= 32, P = I * J and X's row stride multiples of 4 floats (a windowed or padded
+    stride included), X 16-byte aligned, any N >= 1.  A group of fewer than `min_batch` models (None:
+    mnl_many_min_batch of its largest class count, measured) and every model outside the envelope go to
+    their own fit_Adam, as do a 4-D X, a util.HostStream, an instance of the hierarchical subclass
+    and every model under TR_MNL_MANY=0.  report (a dict) receives {'batched': indices, 'alone':
+    indices, 'groups': n, 'x_passes': n}.  verbose=2 and process_group are not offered."""
+    from .util import HostStream
+    models = list(models)
+    M = len(models)
+    _many.check_models(models, CP_logistic_regression, verbose, " of every model")
+    given = dict(lambda_L2=lambda_L2, max_iter=max_iter, tol=tol, patience=patience, Adam_kwargs=Adam_kwargs)
+    args = {k: _many.per_member(k, v, M) for k, v in given.items()}
+    # one class-weight vector is itself a sequence: only a list of sequences (or None) is per model
+    cws = _many.per_member("weights", weights, M,
+                           one_value=lambda v: len(v) > 0 and all(e is not None and np.ndim(e) == 0 for e in v))
+    if min_batch is not None and int(min_batch) < 1:
+        raise ValueError(f"min_batch must be >= 1, got {min_batch}")
+    _many.start_report(report, batched=[], alone=[], groups=0, x_passes=0)
+    if M == 0:
+        return []
+    hps = [adam_hparams(ak) for ak in args["Adam_kwargs"]]  # TypeError on None, as fit_Adam
+    # ---- routing ----
+    by_x, data = {}, {}
+    if _engine.mnl_many_enabled():
+        for j, m in enumerate(models):
+            if type(m) is not CP_logistic_regression or isinstance(m.X, HostStream):
+                continue
+            if not isinstance(m.X, torch.Tensor) or m.X.ndim != 3 or m.X.dtype != torch.float32 or len(m.Bcp) != 3:
+                continue
+            dev, Xd, yd = m._device_data()
+            N, I0, I1 = (int(d) for d in Xd.shape)
+            C, R = int(m.Bcp[-1].shape[0]), int(m.Bcp[0].shape[1])
+            xld = int(Xd.stride(0)) if N > 1 else I0 * I1
+            if Xd.data_ptr() % 16 != 0 or not _engine.mnl_many_envelope(I0, I1, xld, C, R):
+                continue
+            data[j] = (dev, Xd, yd, C, R)
+            by_x.setdefault(_x_key(Xd), []).append(j)
+    groups = []
+    for js in by_x.values():
+        cur, cols = [], 0
+        for j in js:
+            if cols + data[j][3] > _engine.MNL_MANY_MAX_COLS:
+                groups.append(cur)
+                cur, cols = [], 0
+            cur.append(j)
+            cols += data[j][3]
+        groups.append(cur)
+
+    def big_enough(g):
+        need = min_batch if min_batch is not None else mnl_many_min_batch(max(data[j][3] for j in g))
+        return need is not None and len(g) >= int(need)
+    groups = [g for g in groups if big_enough(g)]
+    batched = sorted(j for g in groups for j in g)
+    alone = [j for j in range(M) if j not in set(batched)]
+    results, passes = [False] * M, 0
+    for g in groups:
+        dev, Xd = data[g[0]][0], data[g[0]][1]
+        I0, I1 = int(Xd.shape[1]), int(Xd.shape[2])
+        members, params = [], []
+        for j in g:
+            m = models[j]
+            _, _, yd, C, R = data[j]
+            nn, beta, thr = _engine.nonlin_key(m.non_negative, m.softplus_kwargs, 3)
+            factors = [torch.as_tensor(A) for A in m.Bcp]
+            for f, A in enumerate(factors):
+                if tuple(A.shape) != ((I0, I1, C)[f], R):
+                    raise ValueError(f"model {j}: factor {f} has shape {tuple(A.shape)}, expected {((I0, I1, C)[f], R)}")
+            params.append(factors)
+            cw, W = m._class_weights(cws[j], dev, yd)
+            w = torch.as_tensor(m.weights).to(Xd.device, torch.float32).contiguous()
+            if w.numel() != R:
+                raise ValueError(f"model {j}: weights holds {w.numel()} values, the rank is {R}")
+            members.append(types.SimpleNamespace(
+                y=yd, w=w, cw=cw, W=W, n_classes=C, rank=R, nonneg=nn, beta=beta, thr=thr,
+                lambda_L2=args["lambda_L2"][j], hp=hps[j], max_iter=args["max_iter"][j], tol=args["tol"][j],
+                patience=args["patience"][j], loss_running=m.loss_running))
+        arena, offsets, slices = _many.pack_members(params, Xd.device)
+        for mb, own in zip(members, slices):
+            mb.arena = own
+        stops, n_pass = _engine.run_mnl_many(dev, Xd, members)
+        passes += n_pass
+        _many.unpack_members(arena, offsets, [tuple(models[j].Bcp) for j in g])
+        for j, s in zip(g, stops):
+            results[j] = s > 0
+    for j in alone:  # outside the envelope, a small group or the route switched off: the model's own fit
+        kw = {k: v[j] for k, v in args.items()}
+        if type(models[j]) is CP_logistic_regression or cws[j] is not None:
+            kw["weights"] = cws[j]
+        results[j] = models[j].fit_Adam(verbose=False, **kw)
+    return _many.finish_many(results, verbose, report, batched=batched, alone=alone, groups=len(groups),
+                             x_passes=passes)
