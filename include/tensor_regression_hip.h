@@ -467,6 +467,44 @@ int tr_linear_many_fit(int device, const float* X, int64_t n_rows, int64_t x_row
                        void* table_host, void* table_dev, int64_t table_bytes, void* stream);
 
 /*
+ * Scoring the shared-X linear sweep: up to 16 CP linear models with two or three feature modes scored
+ * over ONE X (n_rows, dims[0], .., dims[n_modes - 1]) float32 at x_row_stride floats (0 = P, the
+ * product of the dims).  Only the forward half of the sweep runs: X is read once and the call makes
+ * five kernel launches whatever the number of members.  Per member, yhat = <X, B> + bias goes to
+ * `yhat` when that is not NULL, and with a target `y` five fp64 sums go to `sums`:
+ *   sums[0] = sum e^2 (e = yhat - y), sums[1] = sum (yhat - k), sums[2] = sum (yhat - k)^2,
+ *   sums[3] = sum (y - k), sums[4] = sum (y - k)^2, with the shift k = y[0]
+ * from which the MSE, the variances and R^2 follow without cancellation.  `params` holds the factors
+ * in mode order, then the bias (tr_linear_member's arena order).
+ * The envelope: 2 or 3 modes, P and the row stride multiples of 4 floats, X 16-byte aligned, rank
+ * 1..32, every dim <= 2^20, P <= 2^30; any n_rows >= 1.  For two modes the forward's split of
+ * (n_rows, P) is the fit's, so yhat and sums[0] carry the bits tr_linear_many_loss_grad works with.
+ * No floating-point atomics; every order depends on the shape alone and a member's bits depend
+ * neither on the other members nor on its position.
+ * The shape and EVERY member are checked before any device call (NULL params or weights, y without
+ * sums, neither yhat nor y, more than 16 members: TR_E_ARG; rank or shape outside the envelope:
+ * TR_E_UNSUPPORTED; tr_last_error() names the member).  n_members == 0 succeeds.
+ */
+typedef struct tr_linear_score_member {
+  const float* params;   /* sum(dims) * rank + 1: the factors in mode order, then the bias */
+  const float* weights;  /* [rank] CP component weights */
+  const float* y;        /* [n_rows] targets; NULL: predict only */
+  float* yhat;           /* [n_rows]; NULL: not wanted */
+  double* sums;          /* [5], required with y */
+  int32_t rank;
+  int32_t nonneg[3];
+  float softplus_beta, softplus_threshold;
+} tr_linear_score_member;
+
+int tr_linear_score_envelope(int n_modes, const int64_t* dims, int64_t x_row_stride, int rank);
+int64_t tr_linear_score_workspace_bytes(int64_t n_rows, int n_modes, const int64_t* dims, int n_members);
+int64_t tr_linear_score_table_bytes(int n_members);
+int tr_linear_many_score(int device, const float* X, int64_t n_rows, int64_t x_row_stride, int n_modes,
+                         const int64_t* dims, const tr_linear_score_member* members, int n_members, void* workspace,
+                         int64_t workspace_bytes, void* table_host, void* table_dev, int64_t table_bytes,
+                         void* stream);
+
+/*
  * Shared-X multinomial sweep: CP multinomial models with two feature modes and a class factor (a
  * hyperparameter grid: one model per grid point) fitted over ONE X (n_rows, I0, I1) float32 at
  * x_row_stride floats (0 = I0 * I1; a stride below I0 * I1 is a windowed view).  No plan is involved.

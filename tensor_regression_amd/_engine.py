@@ -1467,6 +1467,100 @@ def run_linear_many(dev, X, members, sync_every=64, trace=None):
     return stops, 2 * sum(chunks)
 
 
+LINEAR_SCORE_SUMS = 5  # doubles per member: sum e^2, sum (yhat - k), sum (yhat - k)^2, sum (y - k), sum (y - k)^2
+
+
+def linear_score_envelope(dims, x_row_stride, rank):
+    """tr_linear_score_envelope: whether tr_linear_many_score takes these feature dims (needs no device)."""
+    arr = (ctypes.c_int64 * len(dims))(*[int(d) for d in dims])
+    return bool(_lib.load().tr_linear_score_envelope(len(dims), arr, int(x_row_stride), int(rank)))
+
+
+class LinearScoreBuffers:
+    """What the groups of one scoring call need on the device beside the members' arrays: ONE workspace of
+    tr_linear_score_workspace_bytes (the groups run one after another on the stream) and a table segment
+    per group: a group's upload may still be pending when the host builds the next group's table."""
+
+    def __init__(self, dev, N, dims, n_groups):
+        lib = _lib.load()
+        self.dev = dev
+        self.dims = (ctypes.c_int64 * len(dims))(*[int(d) for d in dims])
+        self.ws_bytes = int(lib.tr_linear_score_workspace_bytes(N, len(dims), self.dims, LINEAR_MANY_MAX))
+        if self.ws_bytes <= 0:
+            raise ValueError(f"the linear score does not take the shape ({N}, {', '.join(str(int(d)) for d in dims)})")
+        self.table_bytes = -(-int(lib.tr_linear_score_table_bytes(LINEAR_MANY_MAX)) // 256) * 256
+        with torch.cuda.device(dev):
+            self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=f"cuda:{dev}")
+        self.table_host, self.table_dev = table_buffers(dev, self.table_bytes * max(int(n_groups), 1))
+
+    def tables(self, g):
+        """The (pinned host, device) table segment of group g."""
+        at = g * self.table_bytes
+        return self.table_host[at:at + self.table_bytes], self.table_dev[at:at + self.table_bytes]
+
+
+def run_linear_score(dev, X, members, want, trace=None):
+    """Score CP linear models with two or three feature modes over one X (tr_linear_many_score): groups of
+    up to 16 members in list order, each ONE stream of X and five kernel launches.
+
+    X: (N, I0, I1[, I2]) float32 on cuda:`dev`, samples contiguous, any row stride inside the envelope.
+    `members`: objects with arena and arena_at (a packed float32 tensor and the offset of the member's
+    factors and bias in it), w [R], y [N] float32 on the device (want = 'score'), rank, nonneg (one flag
+    per mode), beta, thr (softplus).  want = 'predict': returns [(N,) float32 ndarray] from one download.
+    want = 'score': returns [float64[5]], the sums of tr_linear_score_member, all groups' in one packed
+    device-to-host copy (40 bytes per member) and one host sync; no yhat is stored.  `trace` (a list, for
+    tools/linear_score_shapes.py) receives (ms between device events around the calls, bytes downloaded)."""
+    if want not in ("predict", "score"):
+        raise ValueError(f"run_linear_score: want must be 'predict' or 'score', got {want!r}")
+    lib = _lib.load()
+    M = len(members)
+    if M == 0:
+        return []
+    device = f"cuda:{dev}"
+    N, dims = int(X.shape[0]), [int(d) for d in X.shape[1:]]
+    P = int(np.prod(dims))
+    xld = int(X.stride(0)) if N > 1 else P
+    starts = list(range(0, M, LINEAR_MANY_MAX))
+    bufs = LinearScoreBuffers(dev, N, dims, len(starts))
+    with torch.cuda.device(dev):
+        if want == "predict":
+            out = torch.empty(M * N, dtype=torch.float32, device=device)
+        else:
+            out = torch.empty(M * LINEAR_SCORE_SUMS, dtype=torch.float64, device=device)
+    arr, rec = member_records(_lib.LinearScoreMember, M)
+    rec["params"] = [mb.arena.data_ptr() + 4 * mb.arena_at for mb in members]
+    rec["weights"] = [mb.w.data_ptr() for mb in members]
+    rec["rank"] = [mb.rank for mb in members]
+    rec["nonneg"] = np.array([[1 if f else 0 for f in list(mb.nonneg[:3]) + [False] * (3 - len(mb.nonneg[:3]))]
+                              for mb in members], dtype=np.int32)
+    rec["softplus_beta"], rec["softplus_threshold"] = [mb.beta for mb in members], [mb.thr for mb in members]
+    if want == "predict":
+        rec["yhat"] = out.data_ptr() + 4 * N * np.arange(M)
+    else:
+        rec["y"] = [mb.y.data_ptr() for mb in members]
+        rec["sums"] = out.data_ptr() + 8 * LINEAR_SCORE_SUMS * np.arange(M)
+    stream = stream_handle(dev)
+    member_bytes = ctypes.sizeof(_lib.LinearScoreMember)
+    with torch.cuda.device(dev):
+        if trace is not None:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+        for g, at in enumerate(starts):
+            n = min(LINEAR_MANY_MAX, M - at)
+            th, td = bufs.tables(g)
+            group = ctypes.cast(ctypes.byref(arr, at * member_bytes), ctypes.POINTER(_lib.LinearScoreMember))
+            check(lib.tr_linear_many_score(dev, ptr(X), N, xld, len(dims), bufs.dims, group, n, ptr(bufs.ws),
+                                           bufs.ws_bytes, ptr(th), ptr(td), bufs.table_bytes, stream),
+                  "tr_linear_many_score")
+        if trace is not None:
+            ev[1].record()
+        host = out.cpu().numpy()  # the one device-to-host copy and host sync of the call
+        if trace is not None:
+            trace.append((ev[0].elapsed_time(ev[1]), host.nbytes))
+    width = N if want == "predict" else LINEAR_SCORE_SUMS
+    return [host[j * width:(j + 1) * width] for j in range(M)]
+
+
 MNL_MANY_MAX_COLS = 64  # columns (classes summed over the members) of one group of the shared-X multinomial sweep
 
 

@@ -62,6 +62,13 @@ class LinearMember(_c.Structure):
                 ("hist_base", _c.c_int64), ("iter", _c.c_int64), ("patience", _c.c_int64), ("tol", _c.c_double)]
 
 
+class LinearScoreMember(_c.Structure):
+    """`tr_linear_score_member`: one member of tr_linear_many_score (fields in the header's order)."""
+    _fields_ = [("params", _vp), ("weights", _vp), ("y", _vp), ("yhat", _vp), ("sums", _vp),
+                ("rank", _c.c_int32), ("nonneg", _c.c_int32 * 3), ("softplus_beta", _c.c_float),
+                ("softplus_threshold", _c.c_float)]
+
+
 class MnlManyMember(_c.Structure):
     """`tr_mnl_many_member`: one member of the tr_mnl_many_* entries (fields in the header's order)."""
     _fields_ = [("params", _vp), ("weights", _vp), ("y", _vp), ("class_weights", _vp), ("exp_avg", _vp),
@@ -146,6 +153,12 @@ SIGNATURES = {
     "tr_linear_many_fit": (_c.c_int, [_c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
                                       _c.POINTER(LinearMember), _c.c_int, _vp, _c.c_int64, _vp, _vp, _c.c_int64,
                                       _vp]),
+    "tr_linear_score_envelope": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_int64), _c.c_int64, _c.c_int]),
+    "tr_linear_score_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int, _c.POINTER(_c.c_int64), _c.c_int]),
+    "tr_linear_score_table_bytes": (_c.c_int64, [_c.c_int]),
+    "tr_linear_many_score": (_c.c_int, [_c.c_int, _vp, _c.c_int64, _c.c_int64, _c.c_int, _c.POINTER(_c.c_int64),
+                                        _c.POINTER(LinearScoreMember), _c.c_int, _vp, _c.c_int64, _vp, _vp,
+                                        _c.c_int64, _vp]),
     "tr_mnl_many_envelope": (_c.c_int, [_c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int]),
     "tr_mnl_many_workspace_bytes": (_c.c_int64, [_c.c_int64, _c.c_int64, _c.c_int64]),
     "tr_mnl_many_member_table_bytes": (_c.c_int64, [_c.c_int]),

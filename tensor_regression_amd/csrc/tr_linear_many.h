@@ -2,7 +2,8 @@
 // feature modes fitted over ONE X, so that an iteration reads X twice whatever the number of models.
 // This header holds the host side: the geometry of a pass (LmGeom: feature slices, row chunks and the
 // carve of the caller's workspace), the device member table (LmMember, built from the public
-// tr_linear_member) and the per-member argument checks.  No HIP dependency: tests/cpp/
+// tr_linear_member) and the per-member argument checks; and the same for the scoring pass, the forward
+// half alone for two or three feature modes (LsGeom, LsWork, LsMember).  No HIP dependency: tests/cpp/
 // linear_many_check.cpp compiles it with the host compiler alone.  The launchers at the end take the
 // stream as void* for the same reason.
 #pragma once
@@ -13,6 +14,7 @@
 
 #include "../../include/tensor_regression_hip.h"
 #include "tr_member_table.h"
+#include "tr_workspace.h"
 
 namespace tr {
 
@@ -55,6 +57,19 @@ struct LmGeom {
   int64_t oBt, oG, oPhi, oDphi, oR, oZ, oD, oGp, bytes;
 };
 
+// The forward's split of (N, P), shared with the scoring pass (LsGeom): about 1024 workgroups (4 per
+// CU) over rows x slices; a slice is at least LM_MIN_SLICE features, so the Z partials stay below 1/32
+// of X's bytes.
+inline void lm_forward_split(int64_t N, int64_t P, int64_t* nrw, int64_t* slice, int64_t* n_slices) {
+  *nrw = (N + LM_FWD_ROWS - 1) / LM_FWD_ROWS;
+  int64_t ns = (1024 + *nrw - 1) / *nrw;
+  const int64_t ns_max = (P + LM_MIN_SLICE - 1) / LM_MIN_SLICE;
+  if (ns > ns_max) ns = ns_max;
+  if (ns < 1) ns = 1;
+  *slice = ((P + ns - 1) / ns + LM_FOLD - 1) / LM_FOLD * LM_FOLD;
+  *n_slices = (P + *slice - 1) / *slice;
+}
+
 inline bool linear_many_geom(int64_t N, int64_t I0, int64_t I1, LmGeom* g) {
   if (N < 1 || N > LM_MAX_ROWS || !linear_many_envelope(I0, I1, 0, 1)) return false;
   LmGeom q;
@@ -64,15 +79,7 @@ inline bool linear_many_geom(int64_t N, int64_t I0, int64_t I1, LmGeom* g) {
   q.I1 = I1;
   q.P = I0 * I1;
   q.npmax = (I0 + I1) * LM_MAX_R;
-  q.nrw = (N + LM_FWD_ROWS - 1) / LM_FWD_ROWS;
-  // forward: about 1024 workgroups (4 per CU) over rows x slices; a slice is at least LM_MIN_SLICE
-  // features, so the Z partials stay below 1/32 of X's bytes
-  int64_t ns = (1024 + q.nrw - 1) / q.nrw;
-  const int64_t ns_max = (q.P + LM_MIN_SLICE - 1) / LM_MIN_SLICE;
-  if (ns > ns_max) ns = ns_max;
-  if (ns < 1) ns = 1;
-  q.slice = ((q.P + ns - 1) / ns + LM_FOLD - 1) / LM_FOLD * LM_FOLD;
-  q.ns = (q.P + q.slice - 1) / q.slice;
+  lm_forward_split(N, q.P, &q.nrw, &q.slice, &q.ns);
   q.nepi = (N + LM_EPI_ROWS - 1) / LM_EPI_ROWS;
   // gradient: about 4096 waves over feature blocks x row chunks
   q.nfw = (q.P + LM_GRAD_FEATS - 1) / LM_GRAD_FEATS;
@@ -197,7 +204,144 @@ inline int build_linear_table(const tr_linear_member* members, int n_members, bo
   return 0;
 }
 
+// ---- scoring: the forward half alone (tr_linear_many_score) ----
+constexpr int LS_SUMS = 5;  // sum e^2, sum (yhat - k), sum (yhat - k)^2, sum (y - k), sum (y - k)^2; k = y[0]
+
+// Two or three feature modes; P, the stride and the rank as linear_many_envelope.
+inline bool linear_score_envelope(int n_modes, const int64_t* dims, int64_t xld, int rank) {
+  if ((n_modes != 2 && n_modes != 3) || dims == nullptr) return false;
+  int64_t P = 1;
+  for (int f = 0; f < n_modes; ++f) {
+    if (dims[f] < 1 || dims[f] > LM_MAX_DIM) return false;
+    if (P > LM_MAX_P / dims[f]) return false;
+    P *= dims[f];
+  }
+  if ((P & 3) != 0) return false;
+  if (xld < 0 || (xld & 3) != 0) return false;
+  return rank >= 1 && rank <= LM_MAX_R;
+}
+
+// A scoring pass over (N, dims): the forward's split is lm_forward_split's, so Z is the fit's bit for
+// bit; nothing of the gradient half (LmGeom's R, G and slabs) is there.
+struct LsGeom {
+  int64_t N, P;
+  int n_modes;
+  int64_t I[3];
+  int64_t isum;      // I0 + I1 (+ I2): the bias sits at params[isum * rank]
+  int64_t npmax;     // isum * LM_MAX_R: a member's phi slot, in floats
+  int64_t nrw, slice, ns, nepi;
+};
+
+inline bool linear_score_geom(int64_t N, int n_modes, const int64_t* dims, LsGeom* g) {
+  if (N < 1 || N > LM_MAX_ROWS || !linear_score_envelope(n_modes, dims, 0, 1)) return false;
+  LsGeom q;
+  std::memset(&q, 0, sizeof(q));
+  q.N = N;
+  q.n_modes = n_modes;
+  q.P = 1;
+  for (int f = 0; f < n_modes; ++f) {
+    q.I[f] = dims[f];
+    q.P *= dims[f];
+    q.isum += dims[f];
+  }
+  q.npmax = q.isum * LM_MAX_R;
+  lm_forward_split(N, q.P, &q.nrw, &q.slice, &q.ns);
+  q.nepi = (N + LM_EPI_ROWS - 1) / LM_EPI_ROWS;
+  if (g != nullptr) *g = q;
+  return true;
+}
+
+// The pieces of the scoring workspace.  dphi is k_lm_prep's second output, which the two-mode pass
+// shares with the fit; the three-mode prepare writes phi alone and the piece is absent.
+struct LsWork {
+  float *Bt, *phi, *dphi, *Z;
+  double* D;
+};
+
+inline void linear_score_carve(const LsGeom& g, LsWork* w, Carver* c) {
+  const size_t npad = (size_t)(g.nepi * LM_EPI_ROWS);
+  c->add(&w->Bt, (size_t)LM_MAX_M * (size_t)g.P * 4);
+  c->add(&w->phi, (size_t)LM_MAX_M * (size_t)g.npmax * 4);
+  c->add_optional(&w->dphi, g.n_modes == 2 ? (size_t)LM_MAX_M * (size_t)g.npmax * 4 : 0);
+  c->add(&w->Z, (size_t)g.ns * npad * LM_MAX_M * 4);
+  c->add(&w->D, (size_t)g.nepi * LM_MAX_M * LS_SUMS * 8);
+}
+
+// What the kernels read of a scoring member beside its LmMember row (params, w, y, rank, nonneg[0..1],
+// beta, thr: the fields k_lm_prep and k_lm_dense read).  The device table is n LmMember rows followed
+// by n LsMember rows.
+struct LsMember {
+  float* yhat;   // NULL: not wanted
+  double* sums;  // LS_SUMS doubles (y != NULL)
+  int nonneg2;   // the third factor's flag
+  int pad;
+};
+
+inline int64_t linear_score_table_bytes(int n_members) {
+  return n_members < 0 ? 0 : (int64_t)n_members * (int64_t)(sizeof(LmMember) + sizeof(LsMember));
+}
+
+inline int check_linear_score_member(const tr_linear_score_member& m, const char** why) {
+  *why = "";
+  if (m.params == nullptr || m.weights == nullptr) {
+    *why = "NULL buffer";
+    return TR_E_ARG;
+  }
+  if (m.y != nullptr && m.sums == nullptr) {
+    *why = "y without sums";
+    return TR_E_ARG;
+  }
+  if (m.y == nullptr && m.yhat == nullptr) {
+    *why = "neither yhat nor y";
+    return TR_E_ARG;
+  }
+  if (m.rank < 1 || m.rank > LM_MAX_R) {
+    *why = "rank outside 1..32";
+    return TR_E_UNSUPPORTED;
+  }
+  return 0;
+}
+
+// build_linear_table's contract: every member is checked, then the two tables are written; nothing is
+// written unless all pass.
+inline int build_linear_score_table(const tr_linear_score_member* members, int n_members, LmMember* table,
+                                    LsMember* ext, int* bad, const char** why) {
+  *bad = -1;
+  *why = "";
+  if (n_members < 0 || n_members > LM_MAX_M) {
+    *why = "n_members outside 0..16";
+    return TR_E_ARG;
+  }
+  for (int j = 0; j < n_members; ++j)
+    if (int rc = check_linear_score_member(members[j], why)) {
+      *bad = j;
+      return rc;
+    }
+  for (int j = 0; j < n_members; ++j) {
+    const tr_linear_score_member& m = members[j];
+    LmMember& t = table[j];
+    std::memset(&t, 0, sizeof(t));
+    t.params = const_cast<float*>(m.params);  // (the scoring kernels only read it)
+    t.w = m.weights;
+    t.y = m.y;
+    t.rank = m.rank;
+    t.nonneg[0] = m.nonneg[0] != 0 ? 1 : 0;
+    t.nonneg[1] = m.nonneg[1] != 0 ? 1 : 0;
+    t.beta = m.softplus_beta;
+    t.thr = m.softplus_threshold;
+    LsMember& e = ext[j];
+    std::memset(&e, 0, sizeof(e));
+    e.yhat = m.yhat;
+    e.sums = m.y != nullptr ? m.sums : nullptr;
+    e.nonneg2 = m.nonneg[2] != 0 ? 1 : 0;
+  }
+  return 0;
+}
+
 // ---- launchers (tr_linear_many.hip); `stream` is a hipStream_t, the return value a hipError_t ----
+// The scoring pass: prepare, dense build, forward, score, sum.  5 launches whatever n_members is.
+int launch_linear_many_score(const LsGeom& g, const float* X, int64_t xld, const LmMember* table, const LsMember* ext,
+                             int n_members, const LsWork& w, void* stream);
 // One evaluation: prepare, forward, epilogue, gradient slabs, slab reduction, fold.  Fills every
 // member's grad arena.  8 launches with the update, whatever n_members is.
 int launch_linear_many_loss_grad(const LmGeom& g, const float* X, int64_t xld, const LmMember* table, int n_members,

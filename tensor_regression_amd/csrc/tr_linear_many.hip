@@ -17,6 +17,13 @@
 // Eight launches per iteration for any M.  No floating-point atomics; every sum has one fixed order
 // that depends on the shape alone (LmGeom), and a member's column of an MFMA tile is computed from its
 // own operands only: its bits depend neither on the other members nor on its position.
+//
+// Scoring (tr_linear_many_score) runs the forward half alone, for two or three feature modes:
+//   k_lm_prep | k_lm_prep3, k_lm_dense | k_lm_dense3, k_lm_forward, then
+//   k_lm_score      yhat = sum_s Zpart + bias (the epilogue's expression), stored when wanted; fp64
+//                   partials of the five shifted sums per (row block, column)   grid (row blocks of 256)
+//   k_lm_score_sum  a member's partials in k_lm_fold's order into its 5 doubles  grid (M)
+// Five launches for any M, X read once.
 #include "tr_linear_many.h"
 
 #include "tr_adam.h"
@@ -430,7 +437,144 @@ __global__ __launch_bounds__(LM_UPD_T) void k_lm_update(const LmMember* __restri
   }
 }
 
+// ---- scoring (tr_linear_many_score): the forward half, then the metrics' sums ----
+
+// k_lm_prep for three feature modes: phi alone (no gradient follows), the third flag from the LsMember row.
+__global__ __launch_bounds__(256) void k_lm_prep3(const LmMember* __restrict__ tab, const LsMember* __restrict__ ext,
+                                                  int64_t I0, int64_t I1, int64_t I2, int64_t npmax,
+                                                  float* __restrict__ phi) {
+  const LmMember& tm = tab[blockIdx.y];
+  const int R = tm.rank;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (I0 + I1 + I2) * R) return;
+  const int f = e >= (I0 + I1) * R ? 2 : (e >= I0 * R ? 1 : 0);
+  const float a = tm.params[e];
+  const bool nn = f == 2 ? ext[blockIdx.y].nonneg2 != 0 : tm.nonneg[f] != 0;
+  phi[(int64_t)blockIdx.y * npmax + e] = nn ? tr_softplus(a, tm.beta, tm.thr) : a;
+}
+
+// k_lm_dense for three feature modes: ((Phi_0 * w) Phi_1) Phi_2, one fmaf chain over the rank
+__global__ __launch_bounds__(256) void k_lm_dense3(const LmMember* __restrict__ tab, int M, int64_t I0, int64_t I1,
+                                                   int64_t I2, int64_t npmax, const float* __restrict__ phi,
+                                                   float* __restrict__ Bt) {
+  const int64_t P = I0 * I1 * I2;
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const int m = blockIdx.y;
+  float s = 0.f;
+  if (m < M) {
+    const LmMember& tm = tab[m];
+    const int R = tm.rank;
+    const int64_t i = p / (I1 * I2), q = p - i * (I1 * I2);
+    const int64_t j = q / I2, k = q - j * I2;
+    const float* __restrict__ F0 = phi + (int64_t)m * npmax + i * R;
+    const float* __restrict__ F1 = phi + (int64_t)m * npmax + (I0 + j) * R;
+    const float* __restrict__ F2 = phi + (int64_t)m * npmax + (I0 + I1 + k) * R;
+    for (int r = 0; r < R; ++r) s = fmaf((F0[r] * tm.w[r]) * F1[r], F2[r], s);
+  }
+  Bt[(int64_t)m * P + p] = s;
+}
+
+// k_lm_epilogue's thread layout and its yhat expression; per (row block, column) LS_SUMS fp64
+// partials, the 16 threads' sums added in rl order.  The sums are shifted by k = y[0] of the member.
+__global__ __launch_bounds__(256) void k_lm_score(const LmMember* __restrict__ tab, const LsMember* __restrict__ ext,
+                                                  int M, int64_t N, int64_t isum, const float* __restrict__ Zpart,
+                                                  int64_t ns, int64_t npad, double* __restrict__ dpart) {
+  __shared__ double sp[LS_SUMS][16][16];
+  const int col = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const bool has = col < M;
+  const float* __restrict__ y = has ? tab[col].y : nullptr;
+  float* __restrict__ yhat = has ? ext[col].yhat : nullptr;
+  const float bias = has ? tab[col].params[isum * tab[col].rank] : 0.f;
+  const double k0 = y != nullptr ? (double)y[0] : 0.0;
+  double acc[LS_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < LM_EPI_ROWS / 16; ++k) {
+    const int64_t row = (int64_t)blockIdx.x * LM_EPI_ROWS + k * 16 + rl;
+    if (row >= N) break;
+    float z = 0.f;
+    for (int64_t s = 0; s < ns; ++s) z += Zpart[(s * npad + row) * LM_MAX_M + col];
+    const float yh = z + bias;
+    if (yhat != nullptr) yhat[row] = yh;
+    if (y != nullptr) {
+      const float yr = y[row];
+      const float e = yh - yr;
+      const double a = (double)yh - k0, b = (double)yr - k0;
+      acc[0] += (double)e * (double)e;
+      acc[1] += a;
+      acc[2] += a * a;
+      acc[3] += b;
+      acc[4] += b * b;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < LS_SUMS; ++q) sp[q][rl][col] = acc[q];
+  __syncthreads();
+  if (threadIdx.x < 16 * LS_SUMS) {
+    const int q = threadIdx.x >> 4;  // (col = threadIdx.x & 15 as above)
+    double a = 0.0;
+    for (int r = 0; r < 16; ++r) a += sp[q][r][col];
+    dpart[((int64_t)blockIdx.x * LM_MAX_M + col) * LS_SUMS + q] = a;
+  }
+}
+
+// One wave per member: the row blocks' partials in k_lm_fold's order (lane l takes the blocks l,
+// l + 64, .. in increasing order, then the wave butterfly), so that sums[0] carries the bits of the
+// sum the fit's data loss is formed from.
+__global__ __launch_bounds__(64) void k_lm_score_sum(const LsMember* __restrict__ ext,
+                                                     const double* __restrict__ dpart, int64_t nepi) {
+  const int m = blockIdx.x;
+  double* __restrict__ out = ext[m].sums;
+  if (out == nullptr) return;
+  const int lane = threadIdx.x;
+  double a[LS_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int64_t k = lane; k < nepi; k += TR_WAVE)
+#pragma unroll
+    for (int q = 0; q < LS_SUMS; ++q) a[q] += dpart[(k * LM_MAX_M + m) * LS_SUMS + q];
+#pragma unroll
+  for (int q = 0; q < LS_SUMS; ++q) a[q] = wv_allreduce_d(a[q]);
+  if (lane < LS_SUMS) {
+    double v = a[0];
+#pragma unroll
+    for (int q = 1; q < LS_SUMS; ++q) v = lane == q ? a[q] : v;
+    out[lane] = v;
+  }
+}
+
 static inline unsigned lm_cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+
+// The first three launches of a two-mode pass, the fit's and the score's alike.
+static void launch_lm_forward2(hipStream_t st, const float* X, int64_t N, int64_t I0, int64_t I1, int64_t xld,
+                               const LmMember* table, int M, int64_t npmax, int64_t nrw, int64_t slice, int64_t ns,
+                               int64_t npad, float* phi, float* dphi, float* Bt, float* Zp) {
+  const int64_t P = I0 * I1;
+  hipLaunchKernelGGL(k_lm_prep, dim3(lm_cdiv(npmax, 256), M), dim3(256), 0, st, table, I0, I1, npmax, phi, dphi);
+  hipLaunchKernelGGL(k_lm_dense, dim3(lm_cdiv(P, 256), LM_MAX_M), dim3(256), 0, st, table, M, I0, I1, npmax, phi, Bt);
+  hipLaunchKernelGGL(k_lm_forward<2>, dim3((unsigned)nrw, (unsigned)ns), dim3(256), 0, st, X, N, P, xld, Bt, slice, Zp,
+                     npad);
+}
+
+int launch_linear_many_score(const LsGeom& g, const float* X, int64_t xld, const LmMember* table, const LsMember* ext,
+                             int n_members, const LsWork& w, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int M = n_members;
+  const int64_t npad = g.nepi * LM_EPI_ROWS;
+  if (xld == 0) xld = g.P;
+  if (g.n_modes == 2) {
+    launch_lm_forward2(st, X, g.N, g.I[0], g.I[1], xld, table, M, g.npmax, g.nrw, g.slice, g.ns, npad, w.phi, w.dphi,
+                       w.Bt, w.Z);
+  } else {
+    hipLaunchKernelGGL(k_lm_prep3, dim3(lm_cdiv(g.npmax, 256), M), dim3(256), 0, st, table, ext, g.I[0], g.I[1],
+                       g.I[2], g.npmax, w.phi);
+    hipLaunchKernelGGL(k_lm_dense3, dim3(lm_cdiv(g.P, 256), LM_MAX_M), dim3(256), 0, st, table, M, g.I[0], g.I[1],
+                       g.I[2], g.npmax, w.phi, w.Bt);
+    hipLaunchKernelGGL(k_lm_forward<2>, dim3((unsigned)g.nrw, (unsigned)g.ns), dim3(256), 0, st, X, g.N, g.P, xld, w.Bt,
+                       g.slice, w.Z, npad);
+  }
+  hipLaunchKernelGGL(k_lm_score, dim3((unsigned)g.nepi), dim3(256), 0, st, table, ext, M, g.N, g.isum, w.Z, g.ns, npad,
+                     w.D);
+  hipLaunchKernelGGL(k_lm_score_sum, dim3(M), dim3(TR_WAVE), 0, st, ext, w.D, g.nepi);
+  return (int)hipGetLastError();
+}
 
 int launch_linear_many_loss_grad(const LmGeom& g, const float* X, int64_t xld, const LmMember* table, int n_members,
                                  void* workspace, void* stream) {
@@ -447,12 +591,7 @@ int launch_linear_many_loss_grad(const LmGeom& g, const float* X, int64_t xld, c
   const int M = n_members;
   const int64_t npad = g.nepi * LM_EPI_ROWS;
   if (xld == 0) xld = g.P;
-  hipLaunchKernelGGL(k_lm_prep, dim3(lm_cdiv(g.npmax, 256), M), dim3(256), 0, st, table, g.I0, g.I1, g.npmax, phi,
-                     dphi);
-  hipLaunchKernelGGL(k_lm_dense, dim3(lm_cdiv(g.P, 256), LM_MAX_M), dim3(256), 0, st, table, M, g.I0, g.I1, g.npmax,
-                     phi, Bt);
-  hipLaunchKernelGGL(k_lm_forward<2>, dim3((unsigned)g.nrw, (unsigned)g.ns), dim3(256), 0, st, X, g.N, g.P, xld, Bt,
-                     g.slice, Zp, npad);
+  launch_lm_forward2(st, X, g.N, g.I0, g.I1, xld, table, M, g.npmax, g.nrw, g.slice, g.ns, npad, phi, dphi, Bt, Zp);
   hipLaunchKernelGGL(k_lm_epilogue, dim3((unsigned)g.nepi), dim3(256), 0, st, table, M, g.N, g.I0 + g.I1, Zp,
                      g.ns, npad, (float)(2.0 / (double)g.N), Rr, dpart);
   hipLaunchKernelGGL(k_lm_grad, dim3(lm_cdiv(g.nfw, 4), (unsigned)g.nch), dim3(256), 0, st, X, g.N, g.P, xld, Rr, g.rpc,

@@ -17,13 +17,14 @@ Differences from the reference (all deliberate):
 """
 import types
 
+import numpy as np
 import torch
 
 from . import _engine, _fit, _lib, _many
 from ._engine import Plan, as_device_f32, adam_hparams, run_adam_fit
 
 __all__ = ["make_BcpInit", "non_neg_fn", "lin_model", "stepwise_model", "L2_penalty",
-           "CP_linear_regression", "fit_Adam_many"]
+           "CP_linear_regression", "fit_Adam_many", "predict_many", "score_many"]
 
 
 ####################################
@@ -450,3 +451,191 @@ def fit_Adam_many(models, X, y, lambda_L2=0.01, max_iter=1000, tol=1e-5, patienc
         results[j] = models[j].fit_Adam(X, ys[j], verbose=False, **{k: v[j] for k, v in args.items()})
     return _many.finish_many(results, verbose, report, batched=batched, alone=alone, groups=len(groups),
                              x_passes=passes)
+
+
+####################################
+###### Scoring many models #########
+####################################
+
+# Groups of fewer models go to the models' own predict.  Measured (tools/linear_score_shapes.py,
+# profiles/linear_score_shapes.txt, DESIGN.md "Scoring the linear sweep"): a group of 1 loses to predict
+# plus host metrics at the notebook's shape (0.88x: the same one stream of X, more host work); 2 is the
+# smallest measured size that wins at both shapes (1.69x and 2.11x).
+LINEAR_SCORE_MIN_BATCH = 2
+
+
+def _np64(t):
+    """A target or prediction as a float64 numpy vector on the host."""
+    if isinstance(t, torch.Tensor):
+        t = t.detach().cpu().numpy()
+    return np.asarray(t, dtype=np.float64).reshape(-1)
+
+
+def _host_metrics(y_hat, y):
+    """{'loss', 'var_ratio', 'r2'} of one prediction in float64 numpy.  N = 1 divides 0 by 0: nan, as the
+    same formulas give in numpy, with no warning."""
+    y_hat, y = _np64(y_hat), _np64(y)
+    n = np.float64(y.shape[0])
+    with np.errstate(all="ignore"):
+        e = y_hat - y
+        dh, dy = y_hat - y_hat.mean(), y - y.mean()
+        sse, syy = np.float64(e @ e), np.float64(dy @ dy)
+        return {"loss": float(sse / n), "var_ratio": float((np.float64(dh @ dh) / (n - 1)) / (syy / (n - 1))),
+                "r2": float(1.0 - sse / syy)}
+
+
+def _metrics_from_sums(s, N):
+    """The same three numbers from tr_linear_many_score's five shifted fp64 sums."""
+    s = np.asarray(s, dtype=np.float64)
+    n = np.float64(N)
+    with np.errstate(all="ignore"):
+        shh = s[2] - s[1] * s[1] / n
+        syy = s[4] - s[3] * s[3] / n
+        return {"loss": float(s[0] / n), "var_ratio": float((shh / (n - 1)) / (syy / (n - 1))),
+                "r2": float(1.0 - s[0] / syy)}
+
+
+def _score_prelude(name, models, X, Bcp, ys, shared_y, min_batch, report):
+    """The argument checks of predict_many and score_many, all before any device work; returns
+    (the Bcp entry per model, min_batch, N)."""
+    M = len(models)
+    for m in models:
+        if not isinstance(m, CP_linear_regression):
+            raise TypeError(f"{name} takes this module's CP_linear_regression objects, got {type(m).__name__}")
+    if Bcp is None:
+        Bcp = [None] * M
+    elif not isinstance(Bcp, (list, tuple)) or len(Bcp) != M:
+        raise ValueError(f"Bcp: a list must hold one value per model ({M}), got "
+                         f"{len(Bcp) if isinstance(Bcp, (list, tuple)) else type(Bcp).__name__}")
+    if min_batch is None:
+        min_batch = LINEAR_SCORE_MIN_BATCH
+    if int(min_batch) < 1:
+        raise ValueError(f"min_batch must be >= 1, got {min_batch}")
+    _many.start_report(report, batched=[], alone=[], groups=0, x_passes=0)
+    if M == 0:
+        return [], int(min_batch), 0
+    if not hasattr(X, "shape"):
+        X = np.asarray(X)
+    N = int(X.shape[0])
+    for j, m in enumerate(models):
+        m._check_dtype()
+        factors = m.Bcp if Bcp[j] is None else Bcp[j]
+        dims = [int(np.shape(A)[0]) for A in factors]
+        if list(X.shape[1:]) != dims:
+            raise ValueError(f"model {j}: Incorrect shapes for inner product along {len(dims)} common modes. "
+                             f"tensor_1.shape={list(X.shape)}, factors={[tuple(np.shape(A)) for A in factors]}")
+        R = int(np.shape(factors[0])[1])
+        if any(tuple(np.shape(A)) != (d, R) for A, d in zip(factors, dims)):
+            raise ValueError(f"model {j}: the factors {[tuple(np.shape(A)) for A in factors]} do not share one rank")
+        nw = int(np.size(m.weights)) if not isinstance(m.weights, torch.Tensor) else int(m.weights.numel())
+        if nw != R:
+            raise ValueError(f"model {j}: weights holds {nw} values, the rank is {R}")
+    if ys is not None:
+        for j, yj in enumerate(ys[:1] if shared_y else ys):
+            shp = tuple(torch.as_tensor(yj).shape) if not isinstance(yj, torch.Tensor) else tuple(yj.shape)
+            if len(shp) != 1 or shp[0] != N:
+                raise ValueError(f"y{'' if shared_y else f'[{j}]'} must be 1-D with len(y) == X.shape[0]; got "
+                                 f"y.shape={shp}, X.shape[0]={N}")
+    return list(Bcp), int(min_batch), N
+
+
+def _score_many(name, models, X, ys, shared_y, Bcp, min_batch, report):
+    """What predict_many (ys None) and score_many share: the prelude, the routing, the grouped call and
+    the models that go alone."""
+    models = list(models)
+    M = len(models)
+    Bcp, min_batch, N = _score_prelude(name, models, X, Bcp, ys, shared_y, min_batch, report)
+    if M == 0:
+        return []
+    # ---- routing ----
+    inside = []
+    grouped = (_engine.linear_many_enabled() and isinstance(X, torch.Tensor) and X.dtype == torch.float32
+               and X.ndim in (3, 4))
+    if grouped:
+        dev = _engine.compute_device(X, models[0].device)
+        X = _engine.as_device_rows(X, dev, torch.float32)
+        dims = [int(d) for d in X.shape[1:]]
+        P = 1
+        for d in dims:
+            P *= d
+        xld = int(X.stride(0)) if N > 1 else P
+        for j, m in enumerate(models):
+            factors = m.Bcp if Bcp[j] is None else Bcp[j]
+            f32 = all(not isinstance(A, torch.Tensor) or A.dtype == torch.float32 for A in factors)
+            if (m.dtype == torch.float32 and f32
+                    and _engine.linear_score_envelope(dims, xld, int(np.shape(factors[0])[1]))):
+                inside.append(j)
+    groups = [inside[k:k + _engine.LINEAR_MANY_MAX] for k in range(0, len(inside), _engine.LINEAR_MANY_MAX)]
+    groups = [g for g in groups if len(g) >= min_batch]
+    batched = [j for g in groups for j in g]
+    alone = [j for j in range(M) if j not in set(batched)]
+    results = [None] * M
+    if batched:
+        y_dev, packed, params, w_dev = {}, {}, [], {}
+        members = []
+        for j in batched:
+            m = models[j]
+            _, factors = _fit.coerce_predict_inputs(X, Bcp[j], m.Bcp, m.device)  # the caller's list as predict's
+            key = (id(m), id(factors))
+            if key not in packed:  # every distinct factor list is packed once
+                packed[key] = len(params)
+                params.append([torch.as_tensor(A) for A in factors] + [torch.as_tensor(m.bias).detach().reshape(-1)[:1]])
+            if id(m) not in w_dev:
+                w_dev[id(m)] = torch.as_tensor(m.weights).to(f"cuda:{dev}", torch.float32).contiguous()
+            nn, beta, thr = _engine.nonlin_key(m.non_negative, m.softplus_kwargs, len(dims))
+            mb = types.SimpleNamespace(slot=packed[key], w=w_dev[id(m)], rank=int(factors[0].shape[1]), nonneg=nn,
+                                       beta=beta, thr=thr, y=None)
+            if ys is not None:
+                ykey = 0 if shared_y else j  # a shared y is uploaded once
+                if ykey not in y_dev:
+                    y_dev[ykey] = as_device_f32(torch.as_tensor(ys[j]), dev, torch.float32)
+                mb.y = y_dev[ykey]
+            members.append(mb)
+        arena, offsets, _ = _many.pack_members(params, f"cuda:{dev}")
+        first = [0]
+        for p in params[:-1]:
+            first.append(first[-1] + len(p))
+        for mb in members:
+            mb.arena, mb.arena_at = arena, offsets[first[mb.slot]]
+        out = _engine.run_linear_score(dev, X, members, "predict" if ys is None else "score")
+        for j, o in zip(batched, out):
+            results[j] = o if ys is None else _metrics_from_sums(o, N)
+    for j in alone:  # outside the envelope, a small group or the route switched off: the model's own predict
+        y_hat = models[j].predict(X, Bcp=Bcp[j])
+        results[j] = y_hat if ys is None else _host_metrics(y_hat, ys[j])
+    if report is not None:
+        report.update(batched=batched, alone=alone, groups=len(groups), x_passes=len(groups))
+    return results
+
+
+def predict_many(models, X, Bcp=None, report=None, min_batch=None):
+    """predict of many CP_linear_regression models over ONE X: [ (N,) float32 ndarray ], entry j equal to
+    `models[j].predict(X, Bcp=Bcp[j])` up to fp32 summation order, with X streamed once per group of up
+    to 16 models instead of once per model.
+
+    models: CP_linear_regression objects of this module; the same object may appear more than once.  X:
+    one device tensor for all of them (a row-contiguous view such as X[n_train:], a strided view or a
+    util.windowed_view included).  Bcp: None, or a list with one entry per model, each None or a factor
+    list handled as predict's Bcp.  The routing, `report` and `min_batch` are score_many's."""
+    return _score_many("predict_many", models, X, None, True, Bcp, min_batch, report)
+
+
+def score_many(models, X, y, report=None, min_batch=None):
+    """Score many CP_linear_regression models over ONE X: [ {'loss', 'var_ratio', 'r2'} ] with
+    loss = mean((y_hat - y)^2), the data loss fit_Adam records; var_ratio = var(y_hat) / var(y) with the
+    unbiased variance, the number verbose=2 prints; r2 = 1 - sum (y_hat - y)^2 / sum (y - mean(y))^2.
+    N = 1 gives what the same numpy formulas give (nan), with no warning.
+
+    y: one (N,) target for all models or a list of len(models) targets.  A model inside the envelope is
+    scored in a group: X a float32 device tensor with row-contiguous samples and two or three feature
+    modes (3-D or 4-D), P and the row stride multiples of 4 floats, the model float32 with rank <= 32.
+    Groups hold up to 16 models in list order and share one X stream each; only five fp64 sums per model
+    (40 bytes) come back, all groups' in one copy, and no y_hat.  A group of fewer than `min_batch` models
+    (None: LINEAR_SCORE_MIN_BATCH) and everything outside the envelope (float64, a numpy X, a
+    util.HostStream, an unaligned P, rank above 32, TR_LINEAR_MANY=0) go to the model's own predict with
+    the metrics formed on the host in float64.  report (a dict) receives {'batched': indices, 'alone':
+    indices, 'groups': n, 'x_passes': n} (x_passes: passes over X made by the groups).  Arguments are
+    checked before any device work."""
+    models = list(models)
+    ys, shared_y = _targets(y, len(models)) if len(models) else ([], True)
+    return _score_many("score_many", models, X, ys, shared_y, None, min_batch, report)
